@@ -25,6 +25,13 @@ iteration).  achieved = algorithmic bytes per launch
 (12 nnz + 8 (n+1) + 8 n + 8 n: val + col + int64 row_ptr + x once + y once)
 divided by the mean SpMV duration measured with HIP events on the solver
 stream inside the timed solves; peak = 8000 GB/s (MI355X HBM3E).
+
+A plain run sets up, warms up, times ``--steps`` solves and prints the result
+line.  ``--dump-outputs DIR`` also writes what the last timed solve returned
+(see ``dump_outputs``).  Everything that takes a run of its own -- the CPU
+baseline, the isolated SpMV and global-sum timings, the device-copy bandwidth
+probe -- is measured only with ``--full`` (``--no-cpu`` and ``--no-copy-probe``
+then skip single legs of it).
 """
 from __future__ import annotations
 
@@ -357,6 +364,32 @@ def spawn_ranks(G, argv):
     return subprocess.call(cmd, env=env)
 
 
+DUMP_SAMPLE = 1 << 22  # entries of x written by --dump-outputs, over all ranks (32 MiB of float64)
+
+
+def dump_outputs(path, x, history, result, rank=0, world=1):
+    """--dump-outputs: what the last timed solve handed back, as float64 .npy
+    files in ``path``: ``x`` (the solution vector; beyond DUMP_SAMPLE // world
+    entries, the entries at a sorted sample of that many indices drawn without
+    replacement by numpy's default_rng(SEED + rank), the same in every run),
+    ``residual_history`` and ``result`` = (iterations, converged reason, final
+    residual norm).  Ranks of a sharded run write their own rows as
+    ``<name>.rank<r>.npy``; all ranks together write at most DUMP_SAMPLE
+    entries of x."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    x = np.asarray(x, dtype=np.float64)
+    cap = DUMP_SAMPLE // max(1, world)
+    if x.size > cap:
+        idx = np.sort(np.random.default_rng(SEED + rank).choice(x.size, size=cap, replace=False))
+        x = x[idx]
+    sfx = f".rank{rank}" if world > 1 else ""
+    np.save(os.path.join(path, f"x{sfx}.npy"), np.ascontiguousarray(x))
+    np.save(os.path.join(path, f"residual_history{sfx}.npy"), np.asarray(history, dtype=np.float64))
+    np.save(os.path.join(path, f"result{sfx}.npy"),
+            np.array([result.its, result.reason, result.rnorm], dtype=np.float64))
+
+
 def _progress(rank, msg):
     """Progress on stderr (rank 0): long configurations stay visibly alive;
     stdout carries only the JSON line."""
@@ -390,8 +423,15 @@ def main():
                     help="block preconditioner (the metric: 2-way 'diagonal'; --system fe with the footing "
                          "config: footing.py's 'undrained')")
     ap.add_argument("--solver", default="gmres", choices=["gmres", "aar"])
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-copy-probe", action="store_true", help="skip the device-copy bandwidth probe")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: the CPU baseline, the isolated SpMV and "
+                         "global-sum timings, the device-copy bandwidth probe")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed solve returned (x, residual history, result) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu", action="store_true",
+                    help="skip --full's CPU baseline (accepted and without effect in a plain run)")
+    ap.add_argument("--no-copy-probe", action="store_true",
+                    help="skip --full's device-copy bandwidth probe (accepted and without effect in a plain run)")
     # default: the CPU baseline solves the benched system itself (N=59: ~20-30 s on the box's 16 cores)
     ap.add_argument("--cpu-N", type=int, default=None)
     ap.add_argument("--cpu-maxit", type=int, default=100)
@@ -515,7 +555,11 @@ def main():
         reasons.append(r.reason)
     dt = time.perf_counter() - t1
     barrier()
+    _progress(rank, f"{args.steps} timed solves: {dt:.3f} s")
     tm = h.timings()
+    if args.dump_outputs and args.steps > 0:
+        dump_outputs(args.dump_outputs, d_x.download(), h.history(), r, rank, world)
+        _progress(rank, f"outputs of the last solve written to {args.dump_outputs}")
     if dist is not None:
         import torch
         t = torch.tensor([dt], dtype=torch.float64)
@@ -540,19 +584,20 @@ def main():
     spmv_avg = tm["spmv_total"] / max(1, tm["spmv_calls"])
     alg_bytes = 12.0 * nnz + 8.0 * (n + 1) + 8.0 * n + 8.0 * n
     achieved = alg_bytes / spmv_avg / 1e9 if spmv_avg > 0 else 0.0
-    iso = h.bench_spmv(d_x.p, d_b.p, 10)
+    iso = h.bench_spmv(d_x.p, d_b.p, 10) if args.full else None
     # latency of the solve's global sums: a CGS step's k+1 dots (k ~ its/2) and a norm
     # (sharded runs only: a single rank's "global" sum is a local reduction)
     gsum_us = ({"dots_40": 1e6 * h.bench_global_sum(40, 50), "norm_1": 1e6 * h.bench_global_sum(1, 50)}
-               if sharded else None)
+               if sharded and args.full else None)
     d16, mat_bytes = h.spmv_layout()
     fmt_bytes = mat_bytes + 8.0 * n + 8.0 * n  # + x once + y once
-    load_rhs()
+    if args.full:
+        load_rhs()
 
     # achievable streaming bandwidth on this box: a 4 GiB
     # device-to-device copy (pls_bench_copy), read + write bytes / time
     copy_gbs = None
-    if rank == 0 and not args.no_copy_probe:
+    if rank == 0 and args.full and not args.no_copy_probe:
         import ctypes as C
         g, gr = C.c_double(), C.c_double()
         Nat.check(Nat.lib().pls_bench_copy(1 << 32, 10, 0, C.byref(g)))
@@ -620,7 +665,7 @@ def main():
                          "stream_gbs_measured": copy_gbs,
                          "kernel": ("k_d16_spmv<4,1,false>" if d16 else "k_sell_spmv<8,1,false>") + " (y = A x, outer MatMult)",
                          "alg_bytes_per_launch": alg_bytes, "mean_launch_s": spmv_avg,
-                         "isolated_spmv_gbs": alg_bytes / iso / 1e9,
+                         "isolated_spmv_gbs": alg_bytes / iso / 1e9 if iso else None,
                          "layout": "SELL-64/D16 (16-bit column deltas)" if d16 else "SELL-64 (int32 columns)",
                          "layout_bytes_per_launch": fmt_bytes,
                          "layout_gbs": fmt_bytes / spmv_avg / 1e9 if spmv_avg > 0 else 0.0},
@@ -628,10 +673,10 @@ def main():
         }
         if any(v == "hypre" for k, v in opts.items() if k.endswith("pc_type")):
             out["hypre_semantics"] = hypre_semantics(opts, world if sharded else 1)
-        if not args.no_cpu and world == 1:
+        if args.full and not args.no_cpu and world == 1:
             _progress(rank, f"cpu baseline on the N={args.cpu_N} sample ...")
             out["cpu_baseline"] = cpu_baseline(args, params, db)
-        print(json.dumps(out))
+        print(json.dumps(out), flush=True)
     d_b.free()
     d_x.free()
     h.destroy()

@@ -9,6 +9,8 @@ maps to the reference's option sets as DESIGN.md §5 states.
 * swelling3d-bjacobi: the headline (2-way, PREONLY + BJACOBI(ILU(0)) 256 / 264
   blocks), N = 59;
 * aar-m5: AAR with depth 5 (BASELINE configs[4]).
+
+Also --dump-outputs (host) and, marked gpu, one small plain run end to end.
 """
 import argparse
 import os
@@ -179,3 +181,127 @@ def test_bench_records_hypre_semantics():
     # default on one rank: BoomerAMG's np = 1 run (no automatic coarsening partitions)
     assert bench.hypre_semantics({"s_pc_type": "hypre"}, 1)["processes"] == "np = 1"
     assert "the most partitions" in bench.hypre_semantics({"pls.hypre_coarsen_chunks": "0"}, 1)["processes"]
+
+
+def test_dump_outputs_writes_a_fixed_sample(tmp_path, monkeypatch):
+    """--dump-outputs: float64 .npy files; a vector longer than DUMP_SAMPLE is
+    written as the same sorted seeded sample of its entries in every call."""
+    import numpy as np
+    assert 8 * bench.DUMP_SAMPLE + (1 << 20) <= 64e6  # x + the short arrays stay under 64 MB
+    monkeypatch.setattr(bench, "DUMP_SAMPLE", 1000)
+    res = argparse.Namespace(its=7, reason=2, rnorm=1.5e-9)
+    hist = np.geomspace(1.0, 1e-9, 8)
+    x = np.arange(5000, dtype=np.float64) ** 0.5
+    bench.dump_outputs(str(tmp_path / "a"), x, hist, res)
+    bench.dump_outputs(str(tmp_path / "b"), x.copy(), hist, res)
+    assert sorted(os.listdir(tmp_path / "a")) == ["residual_history.npy", "result.npy", "x.npy"]
+    xa, xb = np.load(tmp_path / "a" / "x.npy"), np.load(tmp_path / "b" / "x.npy")
+    assert xa.dtype == np.float64 and xa.shape == (1000,) and np.array_equal(xa, xb)
+    idx = np.rint(xa ** 2).astype(np.int64)  # x[i] = sqrt(i): the sampled indices
+    assert np.all(np.diff(idx) > 0) and idx.max() < 5000 and np.array_equal(x[idx], xa)
+    assert np.array_equal(np.load(tmp_path / "a" / "residual_history.npy"), hist)
+    assert np.array_equal(np.load(tmp_path / "a" / "result.npy"), [7.0, 2.0, 1.5e-9])
+    # short vectors are written whole; ranks of a sharded run name their files
+    bench.dump_outputs(str(tmp_path / "c"), x[:10], hist, res, rank=1, world=2)
+    assert np.array_equal(np.load(tmp_path / "c" / "x.rank1.npy"), x[:10])
+
+
+@pytest.mark.parametrize("world", [2, 3, 8])
+def test_dump_outputs_of_a_sharded_run_stay_under_the_cap_in_total(tmp_path, monkeypatch, world):
+    """G ranks share the DUMP_SAMPLE entries of x: each writes a sorted seeded
+    sample of DUMP_SAMPLE // G of its own rows (its own draw, the same in every
+    run), whether it holds a slab (sharded) or the whole vector (replicas)."""
+    import numpy as np
+    monkeypatch.setattr(bench, "DUMP_SAMPLE", 1000)
+    res = argparse.Namespace(its=7, reason=2, rnorm=1.5e-9)
+    hist = np.geomspace(1.0, 1e-9, 8)
+    total, picks = 0, []
+    for rank in range(world):
+        x = (np.arange(5000, dtype=np.float64) + 5000 * rank) ** 0.5  # this rank's rows of sqrt(i)
+        for d in ("a", "b"):
+            bench.dump_outputs(str(tmp_path / d), x, hist, res, rank=rank, world=world)
+        xa = np.load(tmp_path / "a" / f"x.rank{rank}.npy")
+        assert xa.dtype == np.float64 and xa.size == 1000 // world
+        assert np.array_equal(xa, np.load(tmp_path / "b" / f"x.rank{rank}.npy"))
+        idx = np.rint(xa ** 2).astype(np.int64) - 5000 * rank
+        assert np.all(np.diff(idx) > 0) and 0 <= idx.min() and idx.max() < 5000 and np.array_equal(x[idx], xa)
+        picks.append(idx)
+        total += xa.size
+    assert total <= 1000 and not np.array_equal(picks[0], picks[1])
+    assert sorted(os.listdir(tmp_path / "a")) == sorted(
+        f"{n}.rank{r}.npy" for n in ("x", "residual_history", "result") for r in range(world))
+
+
+@pytest.mark.gpu
+def test_plain_run_skips_the_extra_measurements_and_dumps_the_solution(gpu, tmp_path):
+    """A plain run (small N) reports ms_per_step for exactly --steps solves,
+    leaves the --full measurements out, and --dump-outputs holds the solution
+    of the benched system: the same x in two runs, residual history ending at
+    the reported residual norm."""
+    import json
+    import subprocess
+    import numpy as np
+    outs = []
+    for d in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--N", "8", "--steps", "3",
+                            "--warmup", "1", "--blocks-s", "4", "--blocks-fp", "4", "--dump-outputs", str(tmp_path / d)],
+                           capture_output=True, text=True, timeout=120)
+        assert r.returncode == 0, r.stderr[-2000:]
+        outs.append(json.loads(r.stdout.strip().splitlines()[-1]))
+    o = outs[0]
+    assert o["steps"] == 3 and o["timings_s"]["spmv_calls"] == 3 * o["its_per_solve"]  # one A SpMV per outer iteration
+    assert o["ms_per_step"] > 0 and abs(o["value"] - o["its_per_solve"] * 1e3 / o["ms_per_step"]) <= 1e-9 * o["value"]
+    assert "cpu_baseline" not in o and o["roofline"]["isolated_spmv_gbs"] is None
+    assert o["roofline"]["stream_gbs_measured"] is None
+    xa, xb = np.load(tmp_path / "a" / "x.npy"), np.load(tmp_path / "b" / "x.npy")
+    assert xa.dtype == np.float64 and xa.size == o["config"]["dofs"] and np.array_equal(xa, xb)
+    res, hist = np.load(tmp_path / "a" / "result.npy"), np.load(tmp_path / "a" / "residual_history.npy")
+    assert res[0] == o["its_per_solve"] and res[1] in o["reasons"] and hist.size == res[0] + 1
+    assert hist[-1] == res[2] and hist[-1] <= max(1e-6 * hist[0], 1e-8)
+
+
+@pytest.mark.gpu
+def test_full_run_still_measures_what_moved_behind_it(gpu):
+    """--full (small N): the CPU baseline, the isolated SpMV rate and the
+    device-copy probe are in the result line, next to the same headline
+    fields; --no-cpu and --no-copy-probe each leave out their own leg only."""
+    import json
+    import subprocess
+
+    def run(*extra):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--N", "8", "--steps", "2",
+                            "--warmup", "1", "--blocks-s", "4", "--blocks-fp", "4", "--full", *extra],
+                           capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stderr[-2000:]
+        return json.loads(r.stdout.strip().splitlines()[-1])
+
+    o = run()
+    assert o["steps"] == 2 and o["ms_per_step"] > 0 and o["dtype"] == "f64" and o["higher_is_better"] is True
+    assert abs(o["value"] - o["its_per_solve"] * 1e3 / o["ms_per_step"]) <= 1e-9 * o["value"]
+    cpu = o["cpu_baseline"]
+    assert cpu["value"] > 0 and cpu["kind"] == "port" and "cpu_solver.c" in cpu["sample"] and cpu["its"] > 0
+    assert o["roofline"]["isolated_spmv_gbs"] > 0
+    assert o["roofline"]["stream_gbs_measured"]["copy"] > 0 and o["roofline"]["stream_gbs_measured"]["read"] > 0
+    o = run("--no-cpu", "--no-copy-probe")
+    assert "cpu_baseline" not in o and o["roofline"]["stream_gbs_measured"] is None
+    assert o["roofline"]["isolated_spmv_gbs"] > 0
+
+
+def test_tools_gpu_sh_bench_lines_parse():
+    """Every bench.py command line of tools/gpu.sh is accepted by bench.py's
+    argument parser, and the lines that record the --full measurements ask for
+    them.  (Run with a rank count that disagrees with WORLD_SIZE: bench then
+    stops right after parsing, before it touches a GPU.)"""
+    import re
+    import shlex
+    import subprocess
+    text = open(os.path.join(ROOT, "tools", "gpu.sh")).read()
+    lines = [m.group(1) for m in re.finditer(r"python -u bench\.py\b(.*?)(?: ;;)?$", text, re.M)]
+    assert len(lines) >= 11
+    env = dict(os.environ, WORLD_SIZE="3", RANK="0", LOCAL_RANK="0")
+    for ln in lines:
+        argv = shlex.split(ln)
+        assert "--full" in argv, ln
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *argv, "--gpus", "2"], env=env,
+                           capture_output=True, text=True, timeout=60)
+        assert "WORLD_SIZE=3" in r.stderr and "usage:" not in r.stderr, (ln, r.stderr[-500:])

@@ -54,7 +54,7 @@ for s in "$@"; do
       tests=*) run pytest_gpu_sub 1100 python -u -m pytest tests -m gpu -x -v --timeout 300 --timeout-method thread \
                    -p no:cacheprovider -k "${s#tests=}" ;;
       smoke) run smoke 300 python -u -c "import __graft_entry__ as g; g.smoke()" ;;
-      bench) run configs/headline 500 python -u bench.py ;;
+      bench) run configs/headline 500 python -u bench.py --full ;;
       prof) prof prof --steps 2 --warmup 1 --no-cpu ;;
       prof_footing) prof prof_footing --config footing-inexact-ilu --steps 3 --warmup 1 --no-cpu --no-copy-probe ;;
       prof_amg) prof prof_amg --N 27 --inner hypre --steps 2 --warmup 1 --no-cpu --no-copy-probe ;;
@@ -62,21 +62,21 @@ for s in "$@"; do
       prof_fe) prof prof_fe --system fe --N 12 --inner ilu --steps 2 --warmup 1 --no-cpu --no-copy-probe ;;
       prof_fe24) prof prof_fe24 --system fe --N 24 --inner ilu --steps 1 --warmup 1 --maxit 10 --no-cpu --no-copy-probe ;;
       configs)
-        run configs/swelling2d-exact 400 python -u bench.py --config swelling2d-exact --steps 3 --no-copy-probe
-        run configs/footing-inexact-ilu 400 python -u bench.py --config footing-inexact-ilu --steps 2 --no-copy-probe
-        run configs/aar-m5 400 python -u bench.py --config aar-m5 --steps 2 --no-copy-probe
-        run configs/swelling3d-N64 400 python -u bench.py --config swelling3d-bjacobi --N 64 --steps 2 --no-copy-probe --no-cpu ;;
+        run configs/swelling2d-exact 400 python -u bench.py --full --config swelling2d-exact --steps 3 --no-copy-probe
+        run configs/footing-inexact-ilu 400 python -u bench.py --full --config footing-inexact-ilu --steps 2 --no-copy-probe
+        run configs/aar-m5 400 python -u bench.py --full --config aar-m5 --steps 2 --no-copy-probe
+        run configs/swelling3d-N64 400 python -u bench.py --full --config swelling3d-bjacobi --N 64 --steps 2 --no-copy-probe --no-cpu ;;
       fe)
-        run fe/exact2d_2way 300 python -u bench.py --config swelling2d-exact --system fe --steps 20 --warmup 2 --no-copy-probe
-        run fe/exact2d_3way 300 python -u bench.py --config swelling2d-exact --system fe --pc-type "diagonal 3-way" --steps 20 --warmup 2 --no-copy-probe
-        run fe/ilu3d_N12 300 python -u bench.py --system fe --N 12 --inner ilu --steps 5 --warmup 1 --no-copy-probe --cpu-N 6
-        run fe/ilu3d_N20 300 python -u bench.py --system fe --N 20 --inner ilu --steps 3 --warmup 1 --no-copy-probe --no-cpu ;;
+        run fe/exact2d_2way 300 python -u bench.py --full --config swelling2d-exact --system fe --steps 20 --warmup 2 --no-copy-probe
+        run fe/exact2d_3way 300 python -u bench.py --full --config swelling2d-exact --system fe --pc-type "diagonal 3-way" --steps 20 --warmup 2 --no-copy-probe
+        run fe/ilu3d_N12 300 python -u bench.py --full --system fe --N 12 --inner ilu --steps 5 --warmup 1 --no-copy-probe --cpu-N 6
+        run fe/ilu3d_N20 300 python -u bench.py --full --system fe --N 20 --inner ilu --steps 3 --warmup 1 --no-copy-probe --no-cpu ;;
       footing)  # configs[2] on the assembled footing system (lib/fe_footing.py)
-        run fe/footing_N128 600 python -u bench.py --config footing-inexact-ilu --system fe --steps 2 --warmup 1 --no-copy-probe ;;
+        run fe/footing_N128 600 python -u bench.py --full --config footing-inexact-ilu --system fe --steps 2 --warmup 1 --no-copy-probe ;;
       prof_footing_fe) prof prof_footing_fe --config footing-inexact-ilu --system fe --steps 2 --warmup 1 --no-cpu --no-copy-probe ;;
       prof_footing_amg) prof prof_footing_amg --config footing-inexact --system fe --N 12 --steps 1 --warmup 0 --no-cpu --no-copy-probe ;;
       prof_footing128) prof prof_footing128 --config footing-inexact --system fe --N 128 --steps 1 --warmup 0 --no-cpu --no-copy-probe --maxit 40 ;;
-      footing128) run fe/footing_amg_N128 1000 python -u bench.py --config footing-inexact --system fe --N 128 --steps 1 --warmup 0 --no-copy-probe --opt pls.lu_view=1 --opt pls.amg_view=1 --opt pls.ksp_stats=1 ;;
+      footing128) run fe/footing_amg_N128 1000 python -u bench.py --full --config footing-inexact --system fe --N 128 --steps 1 --warmup 0 --no-copy-probe --opt pls.lu_view=1 --opt pls.amg_view=1 --opt pls.ksp_stats=1 ;;
       pmc) run pmc 1300 bash tools/pmc.sh ;;
       custom:*) rest=${s#custom:}; name=${rest%%:*}; cmd=${rest#*:}; run "$name" 1100 bash -c "$cmd" ;;
       *) echo "unknown step $s"; exit 2 ;;
