@@ -97,7 +97,14 @@ int pls_set_device(int device);
  * "pls." are the reference's parameter dict entries ("pls.solver_type gmres",
  * "pls.pc_type diagonal", "pls.inner_ksp_type preonly", ...); every other key
  * is a PETSc options-database entry without its leading '-' ("s_pc_type ilu",
- * "global_ksp_pc_side right", ...), resolved with setFromOptions precedence. */
+ * "global_ksp_pc_side right", ...), resolved with setFromOptions precedence.
+ * KSP types ("pls.solver_type", "pls.inner_ksp_type", "<prefix>ksp_type" for
+ * global_ s_ f_ p_ diff_ fp_ fp_fieldsplit_{0,1}_): gmres, fgmres (right
+ * preconditioning only; "<prefix>ksp_gmres_restart", default 30), cg, bcgs
+ * (left or right), preonly; "pls.solver_type" also takes aar.  Any other type
+ * is an error that lists these.  "pls.bcgs_device 0" keeps BiCGStab's scalars
+ * on the host, "pls.bcgs_fused_reduce 0" gives its sums a final launch of
+ * their own (both bitwise the default).                                      */
 
 /* Build a solver from host CSR matrices in the caller's (e.g. dolfin
  * interleaved) ordering plus the field index sets (sorted global indices of

@@ -288,6 +288,7 @@ struct Handle;
 struct BlockPC : PC {
     Handle *h = nullptr;
     void apply(const double *x, double *y, Ctx &c) override;
+    bool holds_ksp() const override { return true; }
 };
 
 // ========================================================== distribution ===

@@ -842,6 +842,208 @@ void launch_norm2(int64_t n, const double *x, double *partial, double *out, hipS
     k_final<<<1, TPB, 0, st>>>(nb, partial, out, 1);
 }
 
+// ------------------------------------------------------------- BiCGStab --
+// KSPSolve_BCGS (runtime.cpp KSP::solve_bcgs / solve_bcgs_dev).  Both drivers
+// launch these kernels with their coefficients read from the state S on the
+// device, so the iterates round alike whichever driver computed the scalars.
+// Every vector kernel returns at once when *skip (the solve has ended).
+//
+// One thread runs the scalar recurrence; the sums it consumes are in
+// S[BC_SLOT0..].  Same operations as the host driver (IEEE division and
+// square root, no multiply-add pair a compiler could contract).
+__device__ void bcgs_state(int phase, int64_t i, double *S, int64_t *I, double *hist, const BcgsParams &p) {
+    if (I[CG_DONE]) return;
+    auto stop = [&](int reason) {
+        I[CG_REASON] = reason;
+        I[CG_DONE] = 1;
+    };
+    switch (phase) {
+        case BC_MID1: {  // d1 = (v, rp)
+            const double d1 = S[BC_SLOT0];
+            if (d1 == 0.0) return stop(p.r_breakdown);
+            const double alpha = S[BC_RHO] / d1;
+            S[BC_ALPHA] = alpha;
+            S[BC_NEGALPHA] = -alpha;
+            return;
+        }
+        case BC_MID2: {  // d1 = (s, t), d2 = (t, t)
+            const double d1 = S[BC_SLOT0], d2 = S[BC_SLOT1];
+            if (d2 == 0.0) return stop(p.r_pending);  // the host looks at (s, s)
+            const double omega = d1 / d2;
+            S[BC_OMEGA] = omega;
+            S[BC_NEGOMEGA] = -omega;
+            return;
+        }
+        case BC_POST: {  // (r, r) and the next rho = (r, rp); i counts this iteration
+            const double dp = p.c.norm ? sqrt(S[BC_SLOT0]) : 0.0;
+            const double rho = S[BC_RHO];
+            S[BC_RHOOLD] = rho;
+            S[BC_OMEGAOLD] = S[BC_OMEGA];
+            S[BC_RHO] = S[BC_SLOT1];
+            I[CG_ITS] = i + 1;
+            hist[I[CG_HCOUNT]++] = dp;
+            if (p.c.norm) {
+                const int r = cg_conv(p.c, dp, S[BC_RNORM0], S[BC_TTOL]);
+                if (r) return stop(r);
+            }
+            if (rho == 0.0) return stop(p.r_breakdown);
+            if (i + 1 >= p.c.maxit) return stop(p.c.r_its);
+            const double beta = (S[BC_RHO] / S[BC_RHOOLD]) * (S[BC_ALPHA] / S[BC_OMEGAOLD]);
+            S[BC_BETA] = beta;
+            S[BC_C1] = S[BC_OMEGAOLD] * beta;
+            return;
+        }
+    }
+}
+__global__ void k_bcgs_state(int phase, int64_t i, double *S, int64_t *I, double *hist, BcgsParams p) {
+    if (threadIdx.x == 0) bcgs_state(phase, i, S, I, hist, p);
+}
+void launch_bcgs_state(int phase, int64_t i, double *S, int64_t *I, double *hist, const BcgsParams &p,
+                       hipStream_t st) {
+    k_bcgs_state<<<1, 64, 0, st>>>(phase, i, S, I, hist, p);
+}
+
+// End of a reducing kernel: a[r] (valid in thread 0) is this block's part of row r.
+// Without a ticket the parts go to partial[r * nb + block] for k_final.  With
+// one (pls.bcgs_fused_reduce) thread 0 stores them with agent-scope atomic
+// stores (write-through), waits for them, and draws a ticket; the block that
+// draws the last one re-reads every part with agent-scope atomic loads (past
+// its L1), sums them in k_final's order into S[BC_SLOT0 + r], runs the state
+// phase that follows and resets the ticket.  Nobody waits for anybody.
+template <int NR>
+__device__ __forceinline__ void bcgs_finish(const double (&a)[NR], double *partial, double *lds, const BcgsFuse &f) {
+    const int nb = gridDim.x;
+    if (!f.ticket) {
+        if (threadIdx.x == 0) {
+#pragma unroll
+            for (int r = 0; r < NR; ++r) partial[(int64_t)r * nb + blockIdx.x] = a[r];
+        }
+        return;
+    }
+    __shared__ int last;
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int r = 0; r < NR; ++r)
+            __hip_atomic_store(partial + (int64_t)r * nb + blockIdx.x, a[r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        const unsigned t = __hip_atomic_fetch_add(f.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        last = (t == (unsigned)(nb - 1));
+    }
+    __syncthreads();
+    if (!last) return;
+    double tot[NR];
+#pragma unroll
+    for (int r = 0; r < NR; ++r) {
+        double v = 0.0;
+        for (int b = threadIdx.x; b < nb; b += TPB)
+            v += __hip_atomic_load(partial + (int64_t)r * nb + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        tot[r] = block_sum(v, lds);
+    }
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int r = 0; r < NR; ++r) f.S[BC_SLOT0 + r] = tot[r];
+        bcgs_state(f.phase, f.i, f.S, f.I, f.hist, f.p);
+        __hip_atomic_store(f.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
+// p = r - c1 v + c2 p  (c1 = omegaold beta, c2 = beta)
+__global__ __launch_bounds__(TPB) void k_bcgs_p(int64_t n, const double *__restrict__ r, const double *__restrict__ v,
+                                                double *__restrict__ p, const double *S, const int64_t *skip) {
+    if (*skip) return;
+    const double c1 = S[BC_C1], c2 = S[BC_BETA];
+    for (int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x; i < n; i += (int64_t)gridDim.x * TPB)
+        p[i] = (r[i] - c1 * v[i]) + c2 * p[i];
+}
+// w = a x + b y with a = *pa, b = *pb
+__global__ __launch_bounds__(TPB) void k_waxpby_dev(int64_t n, const double *pa, const double *__restrict__ x,
+                                                    const double *pb, const double *__restrict__ y,
+                                                    double *__restrict__ w, const int64_t *skip) {
+    if (*skip) return;
+    const double a = *pa, b = *pb;
+    for (int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x; i < n; i += (int64_t)gridDim.x * TPB)
+        w[i] = a * x[i] + b * y[i];
+}
+// (x, y)
+__global__ __launch_bounds__(TPB) void k_bcgs_dot(int64_t n, const double *__restrict__ x,
+                                                  const double *__restrict__ y, double *partial, BcgsFuse f,
+                                                  const int64_t *skip) {
+    __shared__ double lds[TPB / 64];
+    if (*skip) return;
+    int64_t s, e;
+    chunk_of(n, gridDim.x, blockIdx.x, s, e);
+    double a[1] = {0.0};
+    for (int64_t i = s + threadIdx.x; i < e; i += TPB) a[0] += x[i] * y[i];
+    a[0] = block_sum(a[0], lds);
+    bcgs_finish<1>(a, partial, lds, f);
+}
+// (s, t) and (t, t) in one pass
+__global__ __launch_bounds__(TPB) void k_dot2(int64_t n, const double *__restrict__ sv, const double *__restrict__ tv,
+                                              double *partial, BcgsFuse f, const int64_t *skip) {
+    __shared__ double lds[TPB / 64];
+    if (*skip) return;
+    int64_t s, e;
+    chunk_of(n, gridDim.x, blockIdx.x, s, e);
+    double a[2] = {0.0, 0.0};
+    for (int64_t i = s + threadIdx.x; i < e; i += TPB) {
+        const double ti = tv[i];
+        a[0] += sv[i] * ti;
+        a[1] += ti * ti;
+    }
+    a[0] = block_sum(a[0], lds);
+    a[1] = block_sum(a[1], lds);
+    bcgs_finish<2>(a, partial, lds, f);
+}
+// x += alpha p + omega s, r = s - omega t; (r, r) and (r, rp)
+__global__ __launch_bounds__(TPB) void k_bcgs_update(int64_t n, const double *__restrict__ p,
+                                                     const double *__restrict__ sv, const double *__restrict__ tv,
+                                                     const double *__restrict__ rp, double *__restrict__ x,
+                                                     double *__restrict__ r, double *partial, BcgsFuse f,
+                                                     const int64_t *skip) {
+    __shared__ double lds[TPB / 64];
+    if (*skip) return;
+    const double alpha = f.S[BC_ALPHA], omega = f.S[BC_OMEGA];
+    int64_t s, e;
+    chunk_of(n, gridDim.x, blockIdx.x, s, e);
+    double a[2] = {0.0, 0.0};
+    for (int64_t i = s + threadIdx.x; i < e; i += TPB) {
+        const double si = sv[i];
+        x[i] = (x[i] + alpha * p[i]) + omega * si;
+        const double rn = si - omega * tv[i];
+        r[i] = rn;
+        a[0] += rn * rn;
+        a[1] += rn * rp[i];
+    }
+    a[0] = block_sum(a[0], lds);
+    a[1] = block_sum(a[1], lds);
+    bcgs_finish<2>(a, partial, lds, f);
+}
+
+void launch_bcgs_p(int64_t n, const double *r, const double *v, double *p, const double *S, const int64_t *skip,
+                   hipStream_t st) {
+    if (n > 0) k_bcgs_p<<<stream_grid(n), TPB, 0, st>>>(n, r, v, p, S, skip);
+}
+void launch_waxpby_dev(int64_t n, const double *pa, const double *x, const double *pb, const double *y, double *w,
+                       const int64_t *skip, hipStream_t st) {
+    if (n > 0) k_waxpby_dev<<<stream_grid(n), TPB, 0, st>>>(n, pa, x, pb, y, w, skip);
+}
+void launch_bcgs_dot(int64_t n, const double *x, const double *y, double *partial, const BcgsFuse &f,
+                     const int64_t *skip, hipStream_t st) {
+    k_bcgs_dot<<<reduce_blocks(n), TPB, 0, st>>>(n, x, y, partial, f, skip);
+}
+void launch_dot2(int64_t n, const double *s, const double *t, double *partial, const BcgsFuse &f, const int64_t *skip,
+                 hipStream_t st) {
+    k_dot2<<<reduce_blocks(n), TPB, 0, st>>>(n, s, t, partial, f, skip);
+}
+void launch_bcgs_update(int64_t n, const double *p, const double *s, const double *t, const double *rp, double *x,
+                        double *r, double *partial, const BcgsFuse &f, const int64_t *skip, hipStream_t st) {
+    k_bcgs_update<<<reduce_blocks(n), TPB, 0, st>>>(n, p, s, t, rp, x, r, partial, f, skip);
+}
+// out[j] = sum_b partial[j * nb + b], j < rows (the separate final pass of the kernels above)
+void launch_final(int64_t n, int rows, const double *partial, double *out, hipStream_t st) {
+    k_final<<<rows, TPB, 0, st>>>(reduce_blocks(n), partial, out, 0);
+}
+
 // w -= sum_j h[j] V[:, j] (j ascending, as VecMAXPY); partial ||w||^2.
 // Pairs of rows per thread (16-B loads), eight basis columns loaded ahead of
 // their FMAs so every lane keeps 8-9 loads in flight.

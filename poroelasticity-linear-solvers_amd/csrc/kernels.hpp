@@ -75,6 +75,46 @@ struct CgParams {
     int r_rtol, r_atol, r_dtol, r_nan, r_its, r_indef_pc, r_indef_mat;  // the KSPConvergedReason codes
 };
 void launch_cg_state(int phase, int64_t i, double *S, int64_t *I, double *hist, const CgParams &p, hipStream_t st);
+// BiCGStab (KSP::solve_bcgs / solve_bcgs_dev): scalar state S (doubles), the ints of CgI, and its phases.
+// BC_SLOT0.. receive the sums of the reducing kernels (one, two and two rows).
+enum BcS { BC_RHO, BC_RHOOLD, BC_ALPHA, BC_NEGALPHA, BC_OMEGA, BC_NEGOMEGA, BC_OMEGAOLD, BC_BETA, BC_C1, BC_ONE,
+           BC_RNORM0, BC_TTOL, BC_SLOT0, BC_SLOT1, BC_NS = 16 };
+enum BcPhase { BC_MID1, BC_MID2, BC_POST };
+struct BcgsParams {
+    CgParams c;                 // tolerances, max_it, norm and the reasons of the convergence test
+    int r_breakdown, r_pending;  // r_pending: (t, t) == 0, the driver decides on the host
+};
+// what a reducing kernel does with its block's sums: ticket == nullptr, write them as
+// partials (launch_final and launch_bcgs_state follow); else the last block to arrive
+// sums them into S[BC_SLOT0..], runs state phase `phase` of iteration i and resets the ticket
+struct BcgsFuse {
+    unsigned *ticket;
+    int phase;
+    int64_t i;
+    double *S;
+    int64_t *I;
+    double *hist;
+    BcgsParams p;
+};
+void launch_bcgs_state(int phase, int64_t i, double *S, int64_t *I, double *hist, const BcgsParams &p,
+                       hipStream_t st);
+// p = r - S[BC_C1] v + S[BC_BETA] p
+void launch_bcgs_p(int64_t n, const double *r, const double *v, double *p, const double *S, const int64_t *skip,
+                   hipStream_t st);
+// w = *pa x + *pb y
+void launch_waxpby_dev(int64_t n, const double *pa, const double *x, const double *pb, const double *y, double *w,
+                       const int64_t *skip, hipStream_t st);
+// (x, y) -> row 0
+void launch_bcgs_dot(int64_t n, const double *x, const double *y, double *partial, const BcgsFuse &f,
+                     const int64_t *skip, hipStream_t st);
+// (s, t) -> row 0, (t, t) -> row 1, one pass
+void launch_dot2(int64_t n, const double *s, const double *t, double *partial, const BcgsFuse &f, const int64_t *skip,
+                 hipStream_t st);
+// x += S[BC_ALPHA] p + S[BC_OMEGA] s, r = s - S[BC_OMEGA] t; (r, r) -> row 0, (r, rp) -> row 1
+void launch_bcgs_update(int64_t n, const double *p, const double *s, const double *t, const double *rp, double *x,
+                        double *r, double *partial, const BcgsFuse &f, const int64_t *skip, hipStream_t st);
+// out[j] = sum over blocks of row j of the partials (j < rows), in the fixed order
+void launch_final(int64_t n, int rows, const double *partial, double *out, hipStream_t st);
 // w = a*x + b*y  (out of place)
 void launch_waxpby(int64_t n, double a, const double *x, double b, const double *y, double *w,
                    hipStream_t st);

@@ -311,6 +311,9 @@ struct PC {
     virtual void apply(const double *x, double *y, Ctx &c) = 0;
     // apply() may run on two streams at once (no per-application device state)
     virtual bool reentrant() const { return false; }
+    // apply() runs a KSP of its own (fieldsplit, the block PC): iterations a
+    // device-resident outer loop enqueues past its end would count as inner solves
+    virtual bool holds_ksp() const { return false; }
 };
 struct PCNone : PC {
     explicit PCNone(int64_t n_) { type = "none"; n = n_; }
@@ -547,6 +550,11 @@ struct KSP {
     // work
     DBuf<double> V, w, t1, t2, t3, t4;
     int64_t ldv = 0;  // column stride of the Krylov basis V
+    DBuf<double> Z;   // FGMRES: the preconditioned basis Z_k = M^-1 V_k (restart columns, stride ldv)
+    DBuf<double> t5, t6, t7;  // BiCGStab: with t1..t4, its seven work vectors
+    DBuf<unsigned> bcticket;  // ... the tickets of its single-launch reductions
+    bool bcgs_device = true;  // pls.bcgs_device: BiCGStab's recurrence on the device
+    bool bcgs_fused = true;   // pls.bcgs_fused_reduce: the last block to arrive finishes each sum (one rank only)
     DBuf<double> dh;  // device Hessenberg column / coefficients
     DBuf<double> cgS, cghist;  // device-resident CG: scalar state, residual history
     DBuf<int64_t> cgI;
@@ -569,6 +577,12 @@ struct KSP {
     void solve_gmres(const double *b, double *x, Ctx &c);
     void solve_cg(const double *b, double *x, Ctx &c);
     void solve_cg_dev(const double *b, double *x, Ctx &c);
+    void solve_fgmres(const double *b, double *x, Ctx &c);
+    void solve_bcgs(const double *b, double *x, Ctx &c);
+    void solve_bcgs_dev(const double *b, double *x, Ctx &c);
+    // what the two BiCGStab drivers share: the start (false: ended at iteration 0) and the end
+    bool bcgs_begin(const double *b, double *x, Ctx &c, double &rho0);
+    void bcgs_end(double *x, Ctx &c);
     int converged(int it, double r);
     double rnorm0 = 0, ttol = 0;
 };
@@ -589,6 +603,7 @@ struct PCFieldSplit : PC {
     PCFieldSplit(const DevCSR &M, const std::vector<int32_t> &is0, const std::vector<int32_t> &is1, const Options &o,
                  const std::string &prefix, Ctx &c);
     void apply(const double *x, double *y, Ctx &c) override;
+    bool holds_ksp() const override { return true; }
 };
 
 // PCREDUNDANT: a sharded diagonal block (Halo::l2g) gathered on every rank,

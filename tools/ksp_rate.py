@@ -1,0 +1,89 @@
+"""Time per iteration of an inner s_ Krylov solve on the device.
+
+The 3-D synthetic system (default N = 27), outer right-preconditioned GMRES,
+2-way block PC, the solid block solved by -s_ksp_type <type> with
+-s_pc_type jacobi to -s_ksp_rtol 1e-8 (the other blocks PREONLY + ILU(0)).
+Per variant: one warm-up solve, then --solves timed ones; the time is the
+device-event time of the solid block's solves (pls_timings.pc_solid) over the
+s_ iterations they took (pls_get_ksp_stats).  The variants are run round robin
+(--rounds), so a drift of the shared machine hits all of them alike.  One JSON
+line per (variant, round).
+
+usage: python tools/ksp_rate.py [--N 27] [--variants bcgs_host bcgs_dev bcgs_fused gmres] [--out FILE]
+       --lib PATH   load this libpls.so instead (e.g. another commit's build)
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PKG = os.path.join(ROOT, "poroelasticity-linear-solvers_amd")
+for _p in (ROOT, PKG):
+    if _p not in sys.path:
+        sys.path.insert(0, _p)
+
+VARIANTS = {
+    "bcgs_host": {"s_ksp_type": "bcgs", "pls.bcgs_device": "0"},
+    "bcgs_dev": {"s_ksp_type": "bcgs", "pls.bcgs_device": "1", "pls.bcgs_fused_reduce": "0"},
+    "bcgs_fused": {"s_ksp_type": "bcgs", "pls.bcgs_device": "1", "pls.bcgs_fused_reduce": "1"},
+    "gmres": {"s_ksp_type": "gmres"},
+}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--N", type=int, default=27)
+    ap.add_argument("--variants", nargs="+", default=list(VARIANTS))
+    ap.add_argument("--solves", type=int, default=3)
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--lib", default="")
+    ap.add_argument("--out", default="")
+    a = ap.parse_args()
+    import lib._native as N
+    if a.lib:
+        N.LIB_PATH = os.path.abspath(a.lib)
+    from lib.handle import Handle, params_to_options
+    from oracle import synthetic as S
+    if N.device_count() < 1:
+        raise RuntimeError("ksp_rate: no GPU visible to libpls.so")
+    N.check(N.lib().pls_set_device(0))
+    spec = S.SynthSpec(3, a.N)
+    params = {"solver type": "gmres", "solver atol": 1e-8, "solver rtol": 1e-6, "solver maxiter": 300,
+              "pc type": "diagonal", "inner ksp type": "preonly", "inner pc type": "ilu",
+              "inner accel order": 0, "AAR order": 10, "AAR p": 5, "AAR omega": 1, "AAR beta": 1}
+    base = {"global_ksp_type": "gmres", "global_ksp_pc_side": "right", "s_pc_type": "jacobi", "s_ksp_rtol": "1e-8",
+            "fp_ksp_type": "preonly", "fp_pc_type": "ilu"}
+    b = S.rhs(spec)
+    handles = {}
+    for v in a.variants:
+        opts = dict(base, **VARIANTS[v])
+        opts.update(params_to_options(params))
+        h = Handle.synthetic(spec.dim, spec.N, spec.seed, spec.delta, opts)
+        h.solve(b)  # warm-up: setup, code objects, work vectors
+        handles[v] = h
+    for rnd in range(a.rounds):
+        for v, h in handles.items():
+            h.reset_timings()
+            s0 = h.ksp_stats("s_")
+            its = reason = 0
+            for _ in range(a.solves):
+                _, r = h.solve(b)
+                its, reason = r.its, r.reason
+            s1 = h.ksp_stats("s_")
+            t = h.timings()
+            n_its, n_solves = s1[1] - s0[1], s1[0] - s0[0]
+            line = {"variant": v, "round": rnd, "N": a.N, "ns": int(spec.sizes()[0]), "outer_its": its,
+                    "outer_reason": reason, "s_solves": n_solves, "s_its": n_its,
+                    "pc_solid_s": t["pc_solid"], "us_per_s_it": 1e6 * t["pc_solid"] / max(n_its, 1),
+                    "solver_total_s": t["solver_total"], "lib": a.lib or "this build"}
+            print(json.dumps(line), flush=True)
+            if a.out:
+                with open(a.out, "a") as f:
+                    f.write(json.dumps(line) + "\n")
+
+
+if __name__ == "__main__":
+    main()
