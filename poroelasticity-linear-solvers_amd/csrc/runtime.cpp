@@ -1,13 +1,5 @@
 // runtime.cpp -- device memory, options, timers, operators, preconditioners
-// and PETSc-semantics Krylov solvers of libpls.so.
-//
-// The Krylov algorithms follow PETSc as the reference configures it
-// (reference lib/Solver.py:91-102 for the outer solver, lib/Preconditioner.py:
-// 94-118 for the inner ones): GMRES with classical Gram-Schmidt, Givens
-// rotations, happy-breakdown test and BuildSoln (gmres.c); CG (cg.c);
-// PREONLY; KSPConvergedDefault (iterativ.c).  The scalar recurrences run on the
-// host in double precision without FMA contraction (-ffp-contract=off), exactly
-// as the CPU oracle evaluates them.
+// and the fieldsplit PC of libpls.so.  The Krylov solvers are in ksp.cpp.
 #include "runtime.hpp"
 
 #include "amg_host.hpp"
@@ -21,7 +13,6 @@
 #include <numeric>
 #include <cmath>
 #include <cstdio>
-#include <cstring>
 #include <cstring>
 #include <sstream>
 
@@ -2493,6 +2484,7 @@ struct PCRedundant : PC {
         HIPCHK(hipStreamWaitEvent(c.st, ev_b, 0));
         launch_gather(nloc, mine.p, yg.p, y, c.st);
     }
+    bool holds_ksp() const override { return inner->holds_ksp(); }
 };
 
 std::unique_ptr<PC> make_redundant(const std::string &type, const DevCSR &M, Ctx &c,
@@ -2587,824 +2579,6 @@ std::unique_ptr<PC> make_pc(const std::string &type, const DevCSR &M, const Opti
     throw Error("PC type '" + type + "' (prefix " + prefix +
                 ") is not available in this build (supported: none, jacobi, ilu, bjacobi, lu, gamg, hypre)");
 }
-
-// ================================================================= KSP ===
-void KSP::resolve_side_norm(const std::string &side, const std::string &nt) {
-    // KSPSetUpNorms_Private for the types implemented here
-    if (type == "preonly") {
-        right = false;
-        norm = "none";
-        return;
-    }
-    if (type == "gmres") {
-        std::string s = side;
-        if (s.empty()) s = (nt == "unpreconditioned") ? "right" : "left";
-        std::string nn = nt;
-        if (nn.empty()) nn = (s == "right") ? "unpreconditioned" : "preconditioned";
-        const bool ok = (s == "left" && (nn == "preconditioned" || nn == "none")) ||
-                        (s == "right" && (nn == "unpreconditioned" || nn == "none"));
-        if (!ok) throw Error("KSPGMRES (" + prefix + ") does not support norm " + nn + " with pc side " + s);
-        right = (s == "right");
-        norm = nn;
-        return;
-    }
-    if (type == "fgmres") {
-        // KSPFGMRES: right preconditioning only, the true residual norm (or none)
-        const std::string s = side.empty() ? "right" : side, nn = nt.empty() ? "unpreconditioned" : nt;
-        if (s != "right" || (nn != "unpreconditioned" && nn != "none"))
-            throw Error("KSPFGMRES (" + prefix + ") does not support norm " + nn + " with pc side " + s +
-                        " (right preconditioning with norm unpreconditioned or none only)");
-        right = true;
-        norm = nn;
-        return;
-    }
-    if (type == "bcgs") {
-        // KSPBCGS: left with the preconditioned norm (default) or right with the unpreconditioned one
-        const std::string s = side.empty() ? "left" : side;
-        const std::string nn = nt.empty() ? (s == "right" ? "unpreconditioned" : "preconditioned") : nt;
-        const bool ok = (s == "left" && (nn == "preconditioned" || nn == "none")) ||
-                        (s == "right" && (nn == "unpreconditioned" || nn == "none"));
-        if (!ok) throw Error("KSPBCGS (" + prefix + ") does not support norm " + nn + " with pc side " + s);
-        right = (s == "right");
-        norm = nn;
-        return;
-    }
-    if (type == "cg") {
-        if (!side.empty() && side != "left") throw Error("KSPCG (" + prefix + ") supports only left preconditioning");
-        right = false;
-        norm = nt.empty() ? "preconditioned" : nt;
-        if (norm != "preconditioned" && norm != "unpreconditioned" && norm != "none")
-            throw Error("KSPCG (" + prefix + "): unsupported norm type " + norm);
-        return;
-    }
-    throw Error("KSP type '" + type + "' (prefix " + prefix + ") is not available (supported: gmres, fgmres, cg, bcgs, preonly)");
-}
-
-void KSP::ensure_work(Ctx &c) {
-    if (type == "gmres") {
-        // CGS dots of up to restart + 1 columns: one partial per (column, block)
-        // (the context's default room, 136 columns at the largest grid, overflowed
-        // past ~450 iterations of a 1.3M-row solve)
-        c.ensure_partial(n, restart + 2);
-        if (allocated_k != restart) {
-            ldv = (n + 63) & ~(int64_t)63;  // 512-B aligned columns (16-B loads)
-            V.alloc((size_t)(restart + 1) * ldv);
-            t1.alloc(n);
-            t2.alloc(n);
-            dh.alloc(restart + 4);
-            allocated_k = restart;
-        }
-    } else if (type == "fgmres") {
-        c.ensure_partial(n, restart + 2);
-        if (allocated_k != restart) {
-            ldv = (n + 63) & ~(int64_t)63;  // 512-B aligned columns, V and Z alike
-            V.alloc((size_t)(restart + 1) * ldv);
-            Z.alloc((size_t)restart * ldv);
-            t2.alloc(n);
-            dh.alloc(restart + 4);
-            allocated_k = restart;
-        }
-    } else if (type == "bcgs") {
-        c.ensure_partial(n, 2);
-        if (allocated_k != 0) {
-            for (DBuf<double> *w7 : {&t1, &t2, &t3, &t4, &t5, &t6, &t7}) w7->alloc(n);  // r rp p v s t, one scratch
-            cgS.alloc(BC_NS);
-            cgI.alloc(CG_NI);
-            bcticket.alloc(4);
-            allocated_k = 0;
-        }
-    } else if (type == "cg") {
-        if (allocated_k != 0) {
-            t1.alloc(n);  // r
-            t2.alloc(n);  // z
-            t3.alloc(n);  // p
-            t4.alloc(n);  // w
-            allocated_k = 0;
-        }
-    }
-}
-
-int KSP::converged(int it, double r) {
-    auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    if (it == 0) {
-        rnorm0 = r;
-        ttol = std::max(rtol * rnorm0, atol);
-        if (time_limit > 0) t_start = now();
-    }
-    if (std::isnan(r) || std::isinf(r)) return DIVERGED_NANORINF;
-    if (r <= ttol) return r < atol ? CONVERGED_ATOL : CONVERGED_RTOL;
-    if (r >= dtol * rnorm0) return DIVERGED_DTOL;
-    if (time_limit > 0 && it > 0 && now() - t_start > time_limit) return DIVERGED_TIME_LIMIT;
-    return CONVERGED_ITERATING;
-}
-
-void KSP::solve(const double *b, double *x, Ctx &c) {
-    history.clear();
-    if (type == "preonly") {
-        pc->apply(b, x, c);
-        its = 1;
-        reason = CONVERGED_ITS;
-    } else {
-        ensure_work(c);
-        if (type == "gmres") solve_gmres(b, x, c);
-        else if (type == "cg") {
-            // the device-resident loop unless something needs each iteration on the host
-            if (cg_device && !monitor && time_limit <= 0 && maxit > 0 && maxit <= 10000000) solve_cg_dev(b, x, c);
-            else solve_cg(b, x, c);
-        }
-        else if (type == "fgmres") solve_fgmres(b, x, c);
-        else if (type == "bcgs") {
-            // as CG, and only over a PC without a KSP of its own: the iterations enqueued
-            // past the end would count as inner solves and feed them frozen vectors
-            if (bcgs_device && !monitor && time_limit <= 0 && maxit > 0 && maxit <= 10000000 && !pc->holds_ksp())
-                solve_bcgs_dev(b, x, c);
-            else solve_bcgs(b, x, c);
-        }
-        else throw Error("KSP type " + type + " not available");
-    }
-    stat_its += its;
-    stat_max = std::max<int64_t>(stat_max, its);
-    ++stat_solves;
-    stat_div += reason < 0 ? 1 : 0;
-    if (reason < 0) stat_last_neg = reason;
-    c.check_bounds();
-}
-
-KSP::~KSP() {
-    if (stats && stat_solves)
-        fprintf(stderr, "[ksp %s%s] %lld solves, %lld its (mean %.1f, max %lld)\n", prefix.c_str(), type.c_str(),
-                (long long)stat_solves, (long long)stat_its, (double)stat_its / (double)stat_solves, (long long)stat_max);
-}
-
-void KSP::solve_gmres(const double *b, double *x, Ctx &c) {
-    const int64_t mk = restart;
-    const double haptol = 1e-30;
-    std::vector<double> HH((mk + 1) * (mk + 1), 0.0), cc(mk + 1, 0.0), ss(mk + 1, 0.0), grs(mk + 2, 0.0),
-        nrs(mk + 1, 0.0);
-    auto H = [&](int64_t i, int64_t j) -> double & { return HH[(size_t)i * (mk + 1) + j]; };
-    double *t1p = t1.p, *t2p = t2.p;
-    launch_set(n, 0.0, x, c.st);
-    its = 0;
-    reason = 0;
-    bool first = true;
-    while (!reason) {
-        double *v0 = V.p;
-        if (first) {
-            launch_copy(n, b, right ? v0 : t1p, c.st);
-        } else {
-            A->apply(x, t2p, c);
-            launch_waxpby(n, 1.0, b, -1.0, t2p, right ? v0 : t1p, c.st);
-        }
-        if (!right) pc->apply(t1p, v0, c);
-        double res = c.norm2(n, v0);
-        history.push_back(res);
-        if (monitor) { printf("  %3d KSP Residual norm %.12e\n", its, res); fflush(stdout); }
-        if (res == 0.0) {
-            reason = CONVERGED_ATOL;
-            rnorm = 0.0;
-            break;
-        }
-        launch_scale(n, 1.0 / res, v0, c.st);
-        reason = converged(its, res);
-        rnorm = res;
-        std::fill(HH.begin(), HH.end(), 0.0);
-        grs.assign(mk + 2, 0.0);
-        grs[0] = res;
-        int64_t loc_it = 0;
-        while (!reason && loc_it < mk && its < maxit) {
-            double *vk = V.p + loc_it * ldv;
-            double *vn = V.p + (loc_it + 1) * ldv;
-            if (right) {
-                pc->apply(vk, t1p, c);
-                A->apply(t1p, vn, c);
-            } else {
-                A->apply(vk, t1p, c);
-                pc->apply(t1p, vn, c);
-            }
-            const int k = (int)(loc_it + 1);
-            launch_mdot(n, k, nullptr, V.p, ldv, vn, c.partials(n, k), dh.p, c.st);
-            c.comm->global_sum_dev(dh.p, k, c.st);
-            launch_maxpy_norm(n, k, V.p, ldv, dh.p, -1.0, vn, c.partials(n, 1), dh.p + k, c.st);
-            c.comm->global_sum_dev(dh.p + k, 1, c.st);
-            double *hs = c.host_scalars(k + 1);
-            HIPCHK(hipMemcpyAsync(hs, dh.p, sizeof(double) * (k + 1), hipMemcpyDeviceToHost, c.st));
-            c.sync();
-            for (int j = 0; j < k; ++j) H(j, loc_it) = hs[j];
-            const double tt = std::sqrt(hs[k]);
-            H(loc_it + 1, loc_it) = tt;
-            double hapbnd = std::fabs(tt / grs[loc_it]);
-            if (hapbnd > haptol) hapbnd = haptol;
-            const bool hapend = tt < hapbnd;
-            if (!hapend) launch_scale(n, 1.0 / tt, vn, c.st);
-            // KSPGMRESUpdateHessenberg
-            const int64_t it = loc_it;
-            for (int64_t j = 0; j < it; ++j) {
-                const double t0 = H(j, it);
-                H(j, it) = cc[j] * t0 + ss[j] * H(j + 1, it);
-                H(j + 1, it) = cc[j] * H(j + 1, it) - ss[j] * t0;
-            }
-            if (!hapend) {
-                const double t0 = std::sqrt(H(it, it) * H(it, it) + H(it + 1, it) * H(it + 1, it));
-                if (t0 == 0.0) {
-                    reason = DIVERGED_NULL;
-                    break;
-                }
-                cc[it] = H(it, it) / t0;
-                ss[it] = H(it + 1, it) / t0;
-                grs[it + 1] = -(ss[it] * grs[it]);
-                grs[it] = cc[it] * grs[it];
-                H(it, it) = cc[it] * H(it, it) + ss[it] * H(it + 1, it);
-                res = std::fabs(grs[it + 1]);
-            } else {
-                res = 0.0;
-            }
-            loc_it++;
-            its++;
-            rnorm = res;
-            history.push_back(res);
-            if (monitor) { printf("  %3d KSP Residual norm %.12e\n", its, res); fflush(stdout); }
-            reason = converged(its, res);
-            if (hapend && !reason) {
-                reason = DIVERGED_BREAKDOWN;
-                break;
-            }
-        }
-        // KSPGMRESBuildSoln
-        const int64_t it = loc_it - 1;
-        if (it >= 0) {
-            if (H(it, it) == 0.0) {
-                reason = DIVERGED_BREAKDOWN;
-            } else {
-                nrs[it] = grs[it] / H(it, it);
-                for (int64_t k = it - 1; k >= 0; --k) {
-                    double t0 = grs[k];
-                    for (int64_t j = k + 1; j <= it; ++j) t0 = t0 - H(k, j) * nrs[j];
-                    nrs[k] = t0 / H(k, k);
-                }
-                HIPCHK(hipMemcpyAsync(dh.p, nrs.data(), sizeof(double) * (it + 1), hipMemcpyHostToDevice, c.st));
-                launch_lincomb(n, (int)(it + 1), V.p, ldv, dh.p, t2p, c.st);
-                if (right) {
-                    pc->apply(t2p, t1p, c);
-                    launch_axpby(n, 1.0, t1p, 1.0, x, c.st);
-                } else {
-                    launch_axpby(n, 1.0, t2p, 1.0, x, c.st);
-                }
-                c.sync();  // nrs host buffer reuse
-            }
-        }
-        if (its >= maxit) {
-            if (!reason) reason = DIVERGED_ITS;
-            break;
-        }
-        first = false;
-    }
-}
-
-void KSP::solve_cg(const double *b, double *x, Ctx &c) {
-    double *r = t1.p, *z = t2.p, *p = t3.p, *w = t4.p;
-    launch_set(n, 0.0, x, c.st);
-    launch_copy(n, b, r, c.st);
-    double dp = 0.0;
-    if (norm == "preconditioned") {
-        pc->apply(r, z, c);
-        dp = c.norm2(n, z);
-    } else if (norm == "unpreconditioned") {
-        dp = c.norm2(n, r);
-    }
-    history.push_back(dp);
-    if (monitor) printf("  %3d KSP Residual norm %.12e\n", 0, dp);
-    rnorm = dp;
-    its = 0;
-    reason = (norm != "none") ? converged(0, dp) : 0;
-    if (reason) return;
-    if (norm != "preconditioned") pc->apply(r, z, c);
-    double beta = c.dot(n, z, r), betaold = 0.0, dpi = 0.0, dpiold = 0.0;
-    int64_t i = 0;
-    while (true) {
-        its = (int)(i + 1);
-        if (beta == 0.0) {
-            reason = CONVERGED_ATOL;
-            break;
-        }
-        // cg.c: (z, r) changing sign means an indefinite PC (e.g. ILU(0) of an
-        // undrained solid block with negative pivots): stop with that reason
-        // instead of iterating to max_it
-        if (i > 0 && beta * betaold < 0.0) {
-            reason = DIVERGED_INDEFINITE_PC;
-            break;
-        }
-        if (i == 0) launch_copy(n, z, p, c.st);
-        else launch_axpby(n, 1.0, z, beta / betaold, p, c.st);
-        dpiold = dpi;
-        A->apply(p, w, c);
-        dpi = c.dot(n, p, w);
-        betaold = beta;
-        auto sgn = [](double v) { return (v > 0) - (v < 0); };
-        if (dpi == 0.0 || (i > 0 && sgn(dpi) * sgn(dpiold) < 0)) {
-            reason = DIVERGED_INDEFINITE_MAT;
-            break;
-        }
-        const double a = beta / dpi;
-        launch_axpby(n, a, p, 1.0, x, c.st);
-        launch_axpby(n, -a, w, 1.0, r, c.st);
-        if (norm == "preconditioned") {
-            pc->apply(r, z, c);
-            dp = c.norm2(n, z);
-        } else if (norm == "unpreconditioned") {
-            dp = c.norm2(n, r);
-        } else {
-            dp = 0.0;
-        }
-        rnorm = dp;
-        history.push_back(dp);
-        if (monitor) printf("  %3d KSP Residual norm %.12e\n", (int)(i + 1), dp);
-        if (norm != "none") reason = converged((int)(i + 1), dp);
-        if (reason) break;
-        if (norm != "preconditioned") pc->apply(r, z, c);
-        beta = c.dot(n, z, r);
-        i++;
-        if (i >= maxit) break;
-    }
-    if (i >= maxit && !reason) reason = DIVERGED_ITS;
-}
-
-// KSPSolve_CG with its scalar recurrences on the device (k_cg_state): the
-// start (||r0||, the convergence test's reference, (z, r)) as in solve_cg,
-// then iterations enqueued in batches -- 1 per read-back for the first 32,
-// growing to 8 -- with one read-back of (done, its, reason) per batch instead
-// of three scalar read-backs per iteration.  Iterations enqueued after the
-// solve ended run their products and PC applies on frozen vectors (the vector
-// updates and every state phase check the done flag): x, the iteration count,
-// the reason and the history are those of solve_cg, bit for bit.
-void KSP::solve_cg_dev(const double *b, double *x, Ctx &c) {
-    double *r = t1.p, *z = t2.p, *p = t3.p, *w = t4.p;
-    launch_set(n, 0.0, x, c.st);
-    launch_copy(n, b, r, c.st);
-    double dp = 0.0;
-    if (norm == "preconditioned") {
-        pc->apply(r, z, c);
-        dp = c.norm2(n, z);
-    } else if (norm == "unpreconditioned") {
-        dp = c.norm2(n, r);
-    }
-    history.push_back(dp);
-    if (monitor) printf("  %3d KSP Residual norm %.12e\n", 0, dp);
-    rnorm = dp;
-    its = 0;
-    reason = (norm != "none") ? converged(0, dp) : 0;
-    if (reason) return;
-    if (norm != "preconditioned") pc->apply(r, z, c);
-    const double beta0 = c.dot(n, z, r);
-    if (cgS.n < (size_t)CG_NS) cgS.alloc(CG_NS);
-    if (cgI.n < (size_t)CG_NI) cgI.alloc(CG_NI);
-    if (cghist.n < (size_t)(maxit + 2)) cghist.alloc(maxit + 2);
-    std::vector<double> hs(CG_NS, 0.0);
-    hs[CG_BETA] = beta0;
-    hs[CG_ONE] = 1.0;
-    hs[CG_RNORM0] = rnorm0;
-    hs[CG_TTOL] = ttol;
-    std::vector<int64_t> hi(CG_NI, 0);
-    HIPCHK(hipMemcpyAsync(cgS.p, hs.data(), sizeof(double) * CG_NS, hipMemcpyHostToDevice, c.st));
-    HIPCHK(hipMemcpyAsync(cgI.p, hi.data(), sizeof(int64_t) * CG_NI, hipMemcpyHostToDevice, c.st));
-    c.sync();  // (the host vectors above go out of scope only after the copies)
-    const CgParams prm{rtol, atol, dtol, maxit, norm != "none" ? 1 : 0, CONVERGED_RTOL, CONVERGED_ATOL, DIVERGED_DTOL,
-                       DIVERGED_NANORINF, DIVERGED_ITS, DIVERGED_INDEFINITE_PC, DIVERGED_INDEFINITE_MAT};
-    double *S = cgS.p;
-    int64_t *I = cgI.p;
-    const int64_t *done = I + CG_DONE;
-    auto sum_into = [&](const double *u, const double *v, double *slot) {
-        launch_dot(n, u, v, c.partials(n, 1), slot, c.st);
-        c.comm->global_sum_dev(slot, 1, c.st);
-    };
-    double *hb = c.host_scalars(CG_NI);
-    int64_t i = 0;
-    while (i < maxit) {
-        // (at most 8 per batch: iterations enqueued past the end are wasted work --
-        // batches of 32 cost more than the read-backs they saved, swelling N=80)
-        const int64_t B = std::min<int64_t>(std::clamp<int64_t>(i / 16, 1, 8), maxit - i);
-        for (int64_t k = 0; k < B; ++k, ++i) {
-            launch_cg_state(CG_TOP, i, S, I, cghist.p, prm, c.st);
-            if (i == 0) launch_copy(n, z, p, c.st);
-            else launch_axpby_dev(n, S + CG_ONE, z, S + CG_BB, p, done, c.st);  // p = z + (beta / betaold) p
-            A->apply(p, w, c);
-            sum_into(p, w, S + CG_SLOT);
-            launch_cg_state(CG_MID, i, S, I, cghist.p, prm, c.st);
-            launch_axpby_dev(n, S + CG_A, p, S + CG_ONE, x, done, c.st);     // x += a p
-            launch_axpby_dev(n, S + CG_NEGA, w, S + CG_ONE, r, done, c.st);  // r -= a w
-            if (norm == "preconditioned") {
-                pc->apply(r, z, c);
-                sum_into(z, z, S + CG_SLOT);
-            } else if (norm == "unpreconditioned") {
-                sum_into(r, r, S + CG_SLOT);
-            }
-            launch_cg_state(CG_POST, i, S, I, cghist.p, prm, c.st);
-            if (norm != "preconditioned") pc->apply(r, z, c);
-            sum_into(z, r, S + CG_SLOT2);
-            launch_cg_state(CG_END, i, S, I, cghist.p, prm, c.st);
-        }
-        HIPCHK(hipMemcpyAsync(hb, I, sizeof(int64_t) * CG_NI, hipMemcpyDeviceToHost, c.st));
-        c.sync();
-        int64_t d = 0;
-        std::memcpy(&d, hb + CG_DONE, sizeof(d));
-        if (d) break;
-    }
-    int64_t st[CG_NI];
-    std::memcpy(st, hb, sizeof(st));
-    its = (int)st[CG_ITS];
-    reason = (int)st[CG_REASON];
-    if (st[CG_HCOUNT] > 0) {
-        std::vector<double> hh(st[CG_HCOUNT]);
-        HIPCHK(hipMemcpyAsync(hh.data(), cghist.p, sizeof(double) * hh.size(), hipMemcpyDeviceToHost, c.st));
-        c.sync();
-        history.insert(history.end(), hh.begin(), hh.end());
-        rnorm = hh.back();
-    }
-}
-
-
-// KSPFGMRES: solve_gmres with the preconditioned vectors kept (Z_k = M^-1 V_k,
-// written by the PC straight into column k of Z), so the PC may change from one
-// application to the next: the solution is x += Z y -- no PC application in
-// BuildSoln -- and the Givens estimate is the true residual norm.  Right
-// preconditioning only (resolve_side_norm).  The cycle, the Givens update and
-// the tests are solve_gmres's; PETSc's FGMRES happy-breakdown bound differs
-// from GMRES's only below the 1e-30 cap applied here.
-void KSP::solve_fgmres(const double *b, double *x, Ctx &c) {
-    const int64_t mk = restart;
-    const double haptol = 1e-30;
-    std::vector<double> HH((mk + 1) * (mk + 1), 0.0), cc(mk + 1, 0.0), ss(mk + 1, 0.0), grs(mk + 2, 0.0),
-        nrs(mk + 1, 0.0);
-    auto H = [&](int64_t i, int64_t j) -> double & { return HH[(size_t)i * (mk + 1) + j]; };
-    double *t2p = t2.p;
-    launch_set(n, 0.0, x, c.st);
-    its = 0;
-    reason = 0;
-    bool first = true;
-    while (!reason) {
-        double *v0 = V.p;
-        if (first) {
-            launch_copy(n, b, v0, c.st);
-        } else {
-            A->apply(x, t2p, c);
-            launch_waxpby(n, 1.0, b, -1.0, t2p, v0, c.st);
-        }
-        double res = c.norm2(n, v0);
-        history.push_back(res);
-        if (monitor) { printf("  %3d KSP Residual norm %.12e\n", its, res); fflush(stdout); }
-        if (res == 0.0) {
-            reason = CONVERGED_ATOL;
-            rnorm = 0.0;
-            break;
-        }
-        launch_scale(n, 1.0 / res, v0, c.st);
-        reason = converged(its, res);
-        rnorm = res;
-        std::fill(HH.begin(), HH.end(), 0.0);
-        grs.assign(mk + 2, 0.0);
-        grs[0] = res;
-        int64_t loc_it = 0;
-        while (!reason && loc_it < mk && its < maxit) {
-            double *vk = V.p + loc_it * ldv;
-            double *zk = Z.p + loc_it * ldv;
-            double *vn = V.p + (loc_it + 1) * ldv;
-            pc->apply(vk, zk, c);
-            A->apply(zk, vn, c);
-            const int k = (int)(loc_it + 1);
-            launch_mdot(n, k, nullptr, V.p, ldv, vn, c.partials(n, k), dh.p, c.st);
-            c.comm->global_sum_dev(dh.p, k, c.st);
-            launch_maxpy_norm(n, k, V.p, ldv, dh.p, -1.0, vn, c.partials(n, 1), dh.p + k, c.st);
-            c.comm->global_sum_dev(dh.p + k, 1, c.st);
-            double *hs = c.host_scalars(k + 1);
-            HIPCHK(hipMemcpyAsync(hs, dh.p, sizeof(double) * (k + 1), hipMemcpyDeviceToHost, c.st));
-            c.sync();
-            for (int j = 0; j < k; ++j) H(j, loc_it) = hs[j];
-            const double tt = std::sqrt(hs[k]);
-            H(loc_it + 1, loc_it) = tt;
-            double hapbnd = std::fabs(tt / grs[loc_it]);
-            if (hapbnd > haptol) hapbnd = haptol;
-            const bool hapend = tt < hapbnd;
-            if (!hapend) launch_scale(n, 1.0 / tt, vn, c.st);
-            // KSPFGMRESUpdateHessenberg
-            const int64_t it = loc_it;
-            for (int64_t j = 0; j < it; ++j) {
-                const double t0 = H(j, it);
-                H(j, it) = cc[j] * t0 + ss[j] * H(j + 1, it);
-                H(j + 1, it) = cc[j] * H(j + 1, it) - ss[j] * t0;
-            }
-            if (!hapend) {
-                const double t0 = std::sqrt(H(it, it) * H(it, it) + H(it + 1, it) * H(it + 1, it));
-                if (t0 == 0.0) {
-                    reason = DIVERGED_NULL;
-                    break;
-                }
-                cc[it] = H(it, it) / t0;
-                ss[it] = H(it + 1, it) / t0;
-                grs[it + 1] = -(ss[it] * grs[it]);
-                grs[it] = cc[it] * grs[it];
-                H(it, it) = cc[it] * H(it, it) + ss[it] * H(it + 1, it);
-                res = std::fabs(grs[it + 1]);
-            } else {
-                res = 0.0;
-            }
-            loc_it++;
-            its++;
-            rnorm = res;
-            history.push_back(res);
-            if (monitor) { printf("  %3d KSP Residual norm %.12e\n", its, res); fflush(stdout); }
-            reason = converged(its, res);
-            if (hapend && !reason) {
-                reason = DIVERGED_BREAKDOWN;
-                break;
-            }
-        }
-        // KSPFGMRESBuildSoln: x += Z y
-        const int64_t it = loc_it - 1;
-        if (it >= 0) {
-            if (H(it, it) == 0.0) {
-                reason = DIVERGED_BREAKDOWN;
-            } else {
-                nrs[it] = grs[it] / H(it, it);
-                for (int64_t k = it - 1; k >= 0; --k) {
-                    double t0 = grs[k];
-                    for (int64_t j = k + 1; j <= it; ++j) t0 = t0 - H(k, j) * nrs[j];
-                    nrs[k] = t0 / H(k, k);
-                }
-                HIPCHK(hipMemcpyAsync(dh.p, nrs.data(), sizeof(double) * (it + 1), hipMemcpyHostToDevice, c.st));
-                launch_lincomb(n, (int)(it + 1), Z.p, ldv, dh.p, t2p, c.st);
-                launch_axpby(n, 1.0, t2p, 1.0, x, c.st);
-                c.sync();  // nrs host buffer reuse
-            }
-        }
-        if (its >= maxit) {
-            if (!reason) reason = DIVERGED_ITS;
-            break;
-        }
-        first = false;
-    }
-}
-
-// ------------------------------------------------------------- BiCGStab --
-// KSPSolve_BCGS, zero initial guess.  K = M^-1 A (left, the preconditioned
-// residual's norm) or A M^-1 (right, the true residual's norm; x = M^-1 x at
-// the end).  Work vectors: r t1, rp t2, p t3, v t4, s t5, t t6, scratch t7.
-// Two drivers over the same vector kernels (coefficients read from the device
-// state S): solve_bcgs keeps the scalars on the host, solve_bcgs_dev runs the
-// recurrence on the device as solve_cg_dev does; x, the iteration count, the
-// reason and the history are the same, bit for bit.
-namespace {
-constexpr int BC_PENDING = 1 << 20;  // (t, t) == 0: decided on the host (bcgs_end)
-}
-
-bool KSP::bcgs_begin(const double *b, double *x, Ctx &c, double &rho0) {
-    double *r = t1.p, *rp = t2.p, *p = t3.p, *v = t4.p;
-    launch_set(n, 0.0, x, c.st);
-    if (right) launch_copy(n, b, r, c.st);
-    else pc->apply(b, r, c);
-    const double dp = (norm != "none") ? c.norm2(n, r) : 0.0;
-    history.push_back(dp);
-    if (monitor) printf("  %3d KSP Residual norm %.12e\n", 0, dp);
-    rnorm = dp;
-    its = 0;
-    reason = (norm != "none") ? converged(0, dp) : 0;
-    if (reason) return false;
-    launch_copy(n, r, rp, c.st);
-    launch_set(n, 0.0, p, c.st);
-    launch_set(n, 0.0, v, c.st);
-    rho0 = c.dot(n, r, rp);
-    return true;
-}
-
-void KSP::bcgs_end(double *x, Ctx &c) {
-    double *p = t3.p, *s = t5.p, *tmp = t7.p;
-    if (reason == BC_PENDING) {
-        // t = K s vanished: converged when s did too (x += alpha p), else a breakdown
-        if (c.dot(n, s, s) != 0.0) {
-            reason = DIVERGED_BREAKDOWN;
-        } else {
-            launch_axpby_dev(n, cgS.p + BC_ALPHA, p, cgS.p + BC_ONE, x, nullptr, c.st);
-            its++;
-            history.push_back(0.0);
-            rnorm = 0.0;
-            reason = CONVERGED_RTOL;
-        }
-    }
-    if (right) {
-        pc->apply(x, tmp, c);
-        launch_copy(n, tmp, x, c.st);
-    }
-}
-
-void KSP::solve_bcgs(const double *b, double *x, Ctx &c) {
-    double *r = t1.p, *rp = t2.p, *p = t3.p, *v = t4.p, *s = t5.p, *t = t6.p, *tmp = t7.p;
-    double rho = 0.0;
-    if (!bcgs_begin(b, x, c, rho)) return;
-    double *S = cgS.p;
-    int64_t *I = cgI.p;
-    const int64_t *never = I + CG_DONE;  // stays 0: the host ends this loop
-    double *hs = c.host_scalars(8);      // [0, 2): sums read back, [4, 6): coefficients on their way up
-    {
-        std::vector<double> s0(BC_NS, 0.0);
-        s0[BC_ONE] = 1.0;
-        std::vector<int64_t> i0(CG_NI, 0);
-        HIPCHK(hipMemcpyAsync(S, s0.data(), sizeof(double) * BC_NS, hipMemcpyHostToDevice, c.st));
-        HIPCHK(hipMemcpyAsync(I, i0.data(), sizeof(int64_t) * CG_NI, hipMemcpyHostToDevice, c.st));
-        c.sync();
-    }
-    auto put2 = [&](int slot, double a0, double a1) {  // (the previous upload ran before the last read-back)
-        hs[4] = a0;
-        hs[5] = a1;
-        HIPCHK(hipMemcpyAsync(S + slot, hs + 4, sizeof(double) * 2, hipMemcpyHostToDevice, c.st));
-    };
-    auto sums = [&](int rows) {
-        launch_final(n, rows, c.partials(n, rows), S + BC_SLOT0, c.st);
-        c.comm->global_sum_dev(S + BC_SLOT0, rows, c.st);
-        HIPCHK(hipMemcpyAsync(hs, S + BC_SLOT0, sizeof(double) * rows, hipMemcpyDeviceToHost, c.st));
-        c.sync();
-    };
-    auto K = [&](const double *in, double *out) {
-        if (right) {
-            pc->apply(in, tmp, c);
-            A->apply(tmp, out, c);
-        } else {
-            A->apply(in, tmp, c);
-            pc->apply(tmp, out, c);
-        }
-    };
-    const BcgsFuse nofuse{nullptr, 0, 0, S, I, nullptr, BcgsParams{}};
-    double rhoold = 1.0, alpha = 1.0, omegaold = 1.0;
-    int64_t i = 0;
-    while (true) {
-        const double beta = (rho / rhoold) * (alpha / omegaold);
-        put2(BC_BETA, beta, omegaold * beta);
-        launch_bcgs_p(n, r, v, p, S, never, c.st);
-        K(p, v);
-        launch_bcgs_dot(n, v, rp, c.partials(n, 1), nofuse, never, c.st);
-        sums(1);
-        double d1 = hs[0];
-        if (d1 == 0.0) {
-            reason = DIVERGED_BREAKDOWN;
-            break;
-        }
-        alpha = rho / d1;
-        put2(BC_ALPHA, alpha, -alpha);
-        launch_waxpby_dev(n, S + BC_ONE, r, S + BC_NEGALPHA, v, s, never, c.st);  // s = r - alpha v
-        K(s, t);
-        launch_dot2(n, s, t, c.partials(n, 2), nofuse, never, c.st);
-        sums(2);
-        d1 = hs[0];
-        const double d2 = hs[1];
-        if (d2 == 0.0) {
-            reason = BC_PENDING;
-            break;
-        }
-        const double omega = d1 / d2;
-        put2(BC_OMEGA, omega, -omega);
-        launch_bcgs_update(n, p, s, t, rp, x, r, c.partials(n, 2), nofuse, never, c.st);
-        sums(2);
-        const double dp = (norm != "none") ? std::sqrt(hs[0]) : 0.0;
-        const double rho_this = rho;
-        rhoold = rho;
-        omegaold = omega;
-        rho = hs[1];  // (r, rp): the next iteration's rho
-        its = (int)(i + 1);
-        rnorm = dp;
-        history.push_back(dp);
-        if (monitor) printf("  %3d KSP Residual norm %.12e\n", (int)(i + 1), dp);
-        if (norm != "none") reason = converged((int)(i + 1), dp);
-        if (reason) break;
-        if (rho_this == 0.0) {
-            reason = DIVERGED_BREAKDOWN;
-            break;
-        }
-        i++;
-        if (i >= maxit) {
-            reason = DIVERGED_ITS;
-            break;
-        }
-    }
-    bcgs_end(x, c);
-}
-
-void KSP::solve_bcgs_dev(const double *b, double *x, Ctx &c) {
-    double *r = t1.p, *rp = t2.p, *p = t3.p, *v = t4.p, *s = t5.p, *t = t6.p, *tmp = t7.p;
-    double rho0 = 0.0;
-    if (!bcgs_begin(b, x, c, rho0)) return;
-    if (cghist.n < (size_t)(maxit + 2)) cghist.alloc(maxit + 2);
-    double *S = cgS.p;
-    int64_t *I = cgI.p;
-    const int64_t *done = I + CG_DONE;
-    // one launch per sum only where no global sum has to sit between the final sum and the state
-    const bool fuse = bcgs_fused && c.comm->size == 1;
-    {
-        std::vector<double> s0(BC_NS, 0.0);
-        const double beta = (rho0 / 1.0) * (1.0 / 1.0);
-        s0[BC_RHO] = rho0;
-        s0[BC_RHOOLD] = s0[BC_ALPHA] = s0[BC_OMEGA] = s0[BC_OMEGAOLD] = s0[BC_ONE] = 1.0;
-        s0[BC_BETA] = beta;
-        s0[BC_C1] = 1.0 * beta;
-        s0[BC_RNORM0] = rnorm0;
-        s0[BC_TTOL] = ttol;
-        std::vector<int64_t> i0(CG_NI, 0);
-        HIPCHK(hipMemcpyAsync(S, s0.data(), sizeof(double) * BC_NS, hipMemcpyHostToDevice, c.st));
-        HIPCHK(hipMemcpyAsync(I, i0.data(), sizeof(int64_t) * CG_NI, hipMemcpyHostToDevice, c.st));
-        HIPCHK(hipMemsetAsync(bcticket.p, 0, sizeof(unsigned) * 4, c.st));
-        c.sync();
-    }
-    const BcgsParams prm{CgParams{rtol, atol, dtol, maxit, norm != "none" ? 1 : 0, CONVERGED_RTOL, CONVERGED_ATOL,
-                                  DIVERGED_DTOL, DIVERGED_NANORINF, DIVERGED_ITS, DIVERGED_INDEFINITE_PC,
-                                  DIVERGED_INDEFINITE_MAT},
-                         DIVERGED_BREAKDOWN, BC_PENDING};
-    auto K = [&](const double *in, double *out) {
-        if (right) {
-            pc->apply(in, tmp, c);
-            A->apply(tmp, out, c);
-        } else {
-            A->apply(in, tmp, c);
-            pc->apply(tmp, out, c);
-        }
-    };
-    auto how = [&](int phase, int64_t i, int tk) {
-        return BcgsFuse{fuse ? bcticket.p + tk : nullptr, phase, i, S, I, cghist.p, prm};
-    };
-    auto after = [&](int rows, int phase, int64_t i) {
-        if (fuse) return;
-        launch_final(n, rows, c.partials(n, rows), S + BC_SLOT0, c.st);
-        c.comm->global_sum_dev(S + BC_SLOT0, rows, c.st);
-        launch_bcgs_state(phase, i, S, I, cghist.p, prm, c.st);
-    };
-    double *hb = c.host_scalars(CG_NI);
-    int64_t i = 0;
-    while (i < maxit) {
-        const int64_t B = std::min<int64_t>(std::clamp<int64_t>(i / 16, 1, 8), maxit - i);  // the CG rule
-        for (int64_t k = 0; k < B; ++k, ++i) {
-            launch_bcgs_p(n, r, v, p, S, done, c.st);
-            K(p, v);
-            launch_bcgs_dot(n, v, rp, c.partials(n, 1), how(BC_MID1, i, 0), done, c.st);
-            after(1, BC_MID1, i);
-            launch_waxpby_dev(n, S + BC_ONE, r, S + BC_NEGALPHA, v, s, done, c.st);  // s = r - alpha v
-            K(s, t);
-            launch_dot2(n, s, t, c.partials(n, 2), how(BC_MID2, i, 1), done, c.st);
-            after(2, BC_MID2, i);
-            launch_bcgs_update(n, p, s, t, rp, x, r, c.partials(n, 2), how(BC_POST, i, 2), done, c.st);
-            after(2, BC_POST, i);
-        }
-        HIPCHK(hipMemcpyAsync(hb, I, sizeof(int64_t) * CG_NI, hipMemcpyDeviceToHost, c.st));
-        c.sync();
-        int64_t d = 0;
-        std::memcpy(&d, hb + CG_DONE, sizeof(d));
-        if (d) break;
-    }
-    int64_t st[CG_NI];
-    std::memcpy(st, hb, sizeof(st));
-    its = (int)st[CG_ITS];
-    reason = (int)st[CG_REASON];
-    if (st[CG_HCOUNT] > 0) {
-        std::vector<double> hh(st[CG_HCOUNT]);
-        HIPCHK(hipMemcpyAsync(hh.data(), cghist.p, sizeof(double) * hh.size(), hipMemcpyDeviceToHost, c.st));
-        c.sync();
-        history.insert(history.end(), hh.begin(), hh.end());
-        rnorm = hh.back();
-    }
-    bcgs_end(x, c);
-}
-
-std::unique_ptr<KSP> make_ksp(const std::string &prefix, const Options &o, const DevCSR *Amat, const DevCSR *Pmat,
-                              const std::string &default_ksp, const std::string &default_pc, Ctx &c, double rtol,
-                              double atol, double dtol, int64_t maxit, int64_t restart, PC *external_pc) {
-    auto k = std::make_unique<KSP>();
-    k->prefix = prefix;
-    k->type = o.str(prefix + "ksp_type", default_ksp);
-    k->rtol = o.num(prefix + "ksp_rtol", rtol);
-    k->atol = o.num(prefix + "ksp_atol", atol);
-    k->dtol = o.num(prefix + "ksp_divtol", dtol);
-    k->maxit = o.integer(prefix + "ksp_max_it", maxit);
-    k->restart = o.integer(prefix + "ksp_gmres_restart", restart);
-    k->monitor = o.has(prefix + "ksp_monitor");
-    k->stats = o.flag("pls.ksp_stats", false);
-    k->cg_device = o.flag("pls.cg_device", true);
-    if (prefix == "global_") k->time_limit = o.num("pls.solver_time_limit", 0.0);
-    k->bcgs_device = o.flag("pls.bcgs_device", true);
-    k->bcgs_fused = o.flag("pls.bcgs_fused_reduce", true);
-    if (o.has(prefix + "ksp_gmres_modifiedgramschmidt") && (k->type == "gmres" || k->type == "fgmres"))
-        throw Error(prefix + "ksp_gmres_modifiedgramschmidt: only classical Gram-Schmidt is implemented");
-    k->resolve_side_norm(o.str(prefix + "ksp_pc_side", ""), o.str(prefix + "ksp_norm_type", ""));
-    if (Amat) {
-        k->owned_op = std::make_unique<MatOp>(Amat);
-        k->A = k->owned_op.get();
-        k->n = Amat->nrows;
-    }
-    if (external_pc) {
-        k->pc = external_pc;
-    } else {
-        k->owned_pc = make_pc(o.str(prefix + "pc_type", default_pc), *Pmat, o, prefix, c);
-        k->pc = k->owned_pc.get();
-    }
-    return k;
-}
-
-}  // namespace pls
-
-namespace pls {
 
 // =========================================================== fieldsplit ===
 void upload(const HostCSR &H, DevCSR &M, Ctx &c) {

@@ -1,9 +1,11 @@
 // runtime.hpp -- host runtime of libpls.so: device memory, options database,
 // operators, preconditioners, Krylov solvers, the block preconditioner and
-// AAR.  The Krylov loops run on the host over device-resident vectors; every
-// vector operation is a HIP kernel on one stream, and the only device->host
-// traffic per outer iteration is the handful of scalars the PETSc algorithms
-// branch on (Hessenberg column, norms).
+// AAR.  Every vector operation is a HIP kernel on one stream over
+// device-resident vectors.  GMRES / FGMRES run their loop on the host and read
+// back the handful of scalars the PETSc algorithm branches on per iteration
+// (Hessenberg column, norms); CG and BiCGStab keep their scalar recurrences on
+// the device and read back (done, its, reason) once per batch of iterations,
+// with host-driven loops for the monitor and the time limit (ksp.cpp).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -574,15 +576,24 @@ struct KSP {
     }
   private:
     void ensure_work(Ctx &c);
-    void solve_gmres(const double *b, double *x, Ctx &c);
+    void solve_gmres(const double *b, double *x, Ctx &c);  // gmres and fgmres
     void solve_cg(const double *b, double *x, Ctx &c);
     void solve_cg_dev(const double *b, double *x, Ctx &c);
-    void solve_fgmres(const double *b, double *x, Ctx &c);
     void solve_bcgs(const double *b, double *x, Ctx &c);
     void solve_bcgs_dev(const double *b, double *x, Ctx &c);
-    // what the two BiCGStab drivers share: the start (false: ended at iteration 0) and the end
+    // what the host and the device driver of a type share: the start (false: ended at iteration 0) and the end
+    bool cg_begin(const double *b, double *x, Ctx &c, double &beta);
     bool bcgs_begin(const double *b, double *x, Ctx &c, double &rho0);
     void bcgs_end(double *x, Ctx &c);
+    void bcgs_K(const double *in, double *out, Ctx &c);
+    // the device-resident loops (CG, BiCGStab): may this solve run one, its parameters, its
+    // initial state, and the driver around enqueue(i)
+    bool device_loop_allowed() const;
+    CgParams cg_params() const;
+    void reset_state(const std::vector<double> &s0, bool tickets, Ctx &c);
+    template <class Enqueue>
+    void device_loop(Ctx &c, Enqueue enqueue);
+    int record(int it, double r, bool test = true);  // history, monitor, rnorm; the convergence test's reason
     int converged(int it, double r);
     double rnorm0 = 0, ttol = 0;
 };
