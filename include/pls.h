@@ -104,7 +104,15 @@ int pls_set_device(int device);
  * (left or right), preonly; "pls.solver_type" also takes aar.  Any other type
  * is an error that lists these.  "pls.bcgs_device 0" keeps BiCGStab's scalars
  * on the host, "pls.bcgs_fused_reduce 0" gives its sums a final launch of
- * their own (both bitwise the default).                                      */
+ * their own (both bitwise the default).
+ * gmres and fgmres orthogonalise with classical Gram-Schmidt
+ * ("<prefix>ksp_gmres_classicalgramschmidt", the default), refined as
+ * "<prefix>ksp_gmres_cgs_refinement_type" says (refine_never, the default,
+ * refine_ifneeded, refine_always; anything else is an error), or with modified
+ * Gram-Schmidt ("<prefix>ksp_gmres_modifiedgramschmidt", which wins over the
+ * classical flag, as in PETSc, and ignores the refinement type).  Other KSP
+ * types ignore the three.  "pls.gmres_mgs_fused 1" finishes each modified
+ * Gram-Schmidt sum in the step's own launch (one rank; bitwise the default). */
 
 /* Build a solver from host CSR matrices in the caller's (e.g. dolfin
  * interleaved) ordering plus the field index sets (sorted global indices of
@@ -203,6 +211,12 @@ int pls_reset_timings(pls_handle *h);
  * per solve, summed; the reference's own output is the outer count only,
  * lib/AbstractPhysics.py:77-78), [4] the most recent such reason (0: none).  */
 int pls_get_ksp_stats(pls_handle *h, const char *prefix, int64_t stats[5]);
+/* The orthogonalisation of the gmres / fgmres KSP with this prefix since setup:
+ * stats[0] Arnoldi steps orthogonalised, [1] second classical Gram-Schmidt
+ * passes performed, [2] the scheme (0 CGS refine_never, 1 refine_ifneeded,
+ * 2 refine_always, 3 modified Gram-Schmidt).  An unknown prefix or a KSP of
+ * another type is an error.                                                 */
+int pls_get_gmres_orthog_stats(pls_handle *h, const char *prefix, int64_t stats[3]);
 
 /* Export a device matrix of the handle to host CSR (tests / parity):
  * which: 0 = A, 1 = P, 2 = P_diff (field-major order).  Call once with

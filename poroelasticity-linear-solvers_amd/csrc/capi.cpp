@@ -1703,31 +1703,46 @@ int pls_get_timings(pls_handle *hh, pls_timings *t) {
         t->spmv_calls = H.timers.spmv_calls;
     })
 }
+// the KSP with this options prefix (the outer solver, the blocks', the fp fieldsplit's); `who` names the caller
+static const KSP *find_ksp(Handle &H, const char *prefix, const void *out, const std::string &who) {
+    if (!prefix || !out) throw Error(who + ": null argument");
+    const std::string want(prefix);
+    const KSP *found = nullptr;
+    std::vector<const KSP *> all = {H.ksp_s.get(), H.ksp_f.get(), H.ksp_p.get(), H.ksp_pd.get(), H.ksp_fp.get(),
+                                    H.outer.get()};
+    if (H.ksp_fp && H.ksp_fp->pc)
+        if (const PCFieldSplit *fs = dynamic_cast<const PCFieldSplit *>(H.ksp_fp->pc)) {
+            all.push_back(fs->k0.get());
+            all.push_back(fs->k1.get());
+        }
+    if (H.fs_fp) {
+        all.push_back(H.fs_fp->k0.get());
+        all.push_back(H.fs_fp->k1.get());
+    }
+    for (const KSP *k : all)
+        if (k && k->prefix == want) found = k;
+    if (!found) throw Error(who + ": no inner solver with prefix '" + want + "'");
+    return found;
+}
 int pls_get_ksp_stats(pls_handle *hh, const char *prefix, int64_t *stats) {
     PLS_TRY({
-        Handle &H = *reinterpret_cast<Handle *>(hh);
-        if (!prefix || !stats) throw Error("pls_get_ksp_stats: null argument");
-        const std::string want(prefix);
-        const KSP *found = nullptr;
-        std::vector<const KSP *> all = {H.ksp_s.get(), H.ksp_f.get(), H.ksp_p.get(), H.ksp_pd.get(), H.ksp_fp.get(),
-                                        H.outer.get()};
-        if (H.ksp_fp && H.ksp_fp->pc)
-            if (const PCFieldSplit *fs = dynamic_cast<const PCFieldSplit *>(H.ksp_fp->pc)) {
-                all.push_back(fs->k0.get());
-                all.push_back(fs->k1.get());
-            }
-        if (H.fs_fp) {
-            all.push_back(H.fs_fp->k0.get());
-            all.push_back(H.fs_fp->k1.get());
-        }
-        for (const KSP *k : all)
-            if (k && k->prefix == want) found = k;
-        if (!found) throw Error("pls_get_ksp_stats: no inner solver with prefix '" + want + "'");
+        const KSP *found = find_ksp(*reinterpret_cast<Handle *>(hh), prefix, stats, "pls_get_ksp_stats");
         stats[0] = found->stat_solves;
         stats[1] = found->stat_its;
         stats[2] = found->stat_max;
         stats[3] = found->stat_div;
         stats[4] = found->stat_last_neg;
+    })
+}
+int pls_get_gmres_orthog_stats(pls_handle *hh, const char *prefix, int64_t *stats) {
+    PLS_TRY({
+        const KSP *found = find_ksp(*reinterpret_cast<Handle *>(hh), prefix, stats, "pls_get_gmres_orthog_stats");
+        if (found->type != "gmres" && found->type != "fgmres")
+            throw Error("pls_get_gmres_orthog_stats: the solver with prefix '" + found->prefix + "' is of type " +
+                        found->type + ", not gmres or fgmres");
+        stats[0] = found->stat_orth_steps;
+        stats[1] = found->stat_orth_second;
+        stats[2] = found->orthog;
     })
 }
 int pls_reset_timings(pls_handle *hh) { PLS_TRY(reinterpret_cast<Handle *>(hh)->timers.reset()) }

@@ -903,13 +903,46 @@ void launch_bcgs_state(int phase, int64_t i, double *S, int64_t *I, double *hist
     k_bcgs_state<<<1, 64, 0, st>>>(phase, i, S, I, hist, p);
 }
 
-// End of a reducing kernel: a[r] (valid in thread 0) is this block's part of row r.
-// Without a ticket the parts go to partial[r * nb + block] for k_final.  With
-// one (pls.bcgs_fused_reduce) thread 0 stores them with agent-scope atomic
+// End of a reducing kernel, single launch: a[r] (valid in thread 0) is this
+// block's part of row r.  Thread 0 stores the parts with agent-scope atomic
 // stores (write-through), waits for them, and draws a ticket; the block that
 // draws the last one re-reads every part with agent-scope atomic loads (past
-// its L1), sums them in k_final's order into S[BC_SLOT0 + r], runs the state
-// phase that follows and resets the ticket.  Nobody waits for anybody.
+// its L1) and sums them in k_final's order.  True (in every thread) in that
+// block alone, with the totals valid in its thread 0; the caller consumes them
+// and calls ticket_reset.  Nobody waits for anybody.  Shared by BiCGStab
+// (bcgs_finish) and the MGS step of GMRES (k_mgs_step).
+template <int NR>
+__device__ __forceinline__ bool ticket_totals(const double (&a)[NR], double *partial, double *lds, unsigned *ticket,
+                                              double (&tot)[NR]) {
+    const int nb = gridDim.x;
+    __shared__ int last;
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int r = 0; r < NR; ++r)
+            __hip_atomic_store(partial + (int64_t)r * nb + blockIdx.x, a[r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        const unsigned t = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        last = (t == (unsigned)(nb - 1));
+    }
+    __syncthreads();
+    if (!last) return false;
+#pragma unroll
+    for (int r = 0; r < NR; ++r) {
+        double v = 0.0;
+        for (int b = threadIdx.x; b < nb; b += TPB)
+            v += __hip_atomic_load(partial + (int64_t)r * nb + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        tot[r] = block_sum(v, lds);
+    }
+    return true;
+}
+__device__ __forceinline__ void ticket_reset(unsigned *ticket) {
+    __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// BiCGStab's end of a reducing kernel.  Without a ticket the parts go to
+// partial[r * nb + block] for k_final.  With one (pls.bcgs_fused_reduce) the
+// last block to arrive (ticket_totals) writes the sums into S[BC_SLOT0 + r]
+// and runs the state phase that follows.
 template <int NR>
 __device__ __forceinline__ void bcgs_finish(const double (&a)[NR], double *partial, double *lds, const BcgsFuse &f) {
     const int nb = gridDim.x;
@@ -920,30 +953,13 @@ __device__ __forceinline__ void bcgs_finish(const double (&a)[NR], double *parti
         }
         return;
     }
-    __shared__ int last;
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int r = 0; r < NR; ++r)
-            __hip_atomic_store(partial + (int64_t)r * nb + blockIdx.x, a[r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        const unsigned t = __hip_atomic_fetch_add(f.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        last = (t == (unsigned)(nb - 1));
-    }
-    __syncthreads();
-    if (!last) return;
     double tot[NR];
-#pragma unroll
-    for (int r = 0; r < NR; ++r) {
-        double v = 0.0;
-        for (int b = threadIdx.x; b < nb; b += TPB)
-            v += __hip_atomic_load(partial + (int64_t)r * nb + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        tot[r] = block_sum(v, lds);
-    }
+    if (!ticket_totals<NR>(a, partial, lds, f.ticket, tot)) return;
     if (threadIdx.x == 0) {
 #pragma unroll
         for (int r = 0; r < NR; ++r) f.S[BC_SLOT0 + r] = tot[r];
         bcgs_state(f.phase, f.i, f.S, f.I, f.hist, f.p);
-        __hip_atomic_store(f.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        ticket_reset(f.ticket);
     }
 }
 
@@ -1138,6 +1154,93 @@ void launch_maxpy_norm(int64_t n, int k, const double *V, int64_t ldv, const dou
     const int nb = reduce_blocks(n);
     k_maxpy_norm<<<nb, TPB, 0, st>>>(n, k, V, ldv, h_dev, w, out ? partial : nullptr);
     if (out) k_final<<<1, TPB, 0, st>>>(nb, partial, out, 0);  // ||w||^2 (rank-local)
+}
+
+// One step of modified Gram-Schmidt (KSPGMRESModifiedGramSchmidtOrthogonalization):
+// w -= (*hprev) vprev first (vprev != null), then this block's part of (w, vj)
+// over the updated rows -- (w, w) when vj is null.  k_mdot's data path: chunks
+// on even rows, 16-B loads of row pairs, two pairs per trip with their loads
+// ahead of the FMAs, the odd tail row in thread 0.  Every row is read and
+// written by one thread of one block, so no block depends on another's rows.
+// With a ticket the last block to arrive sums the parts (ticket_totals, in
+// k_final's order) into *out, where the next step's launch reads its
+// coefficient; without one they go to partial[block] for k_final.
+__global__ __launch_bounds__(TPB) void k_mgs_step(int64_t n, const double *__restrict__ vprev,
+                                                  const double *__restrict__ hprev, const double *__restrict__ vj,
+                                                  double *w, double *partial, double *out, unsigned *ticket) {
+    __shared__ double lds[TPB / 64];
+    int64_t s, e;
+    chunk_even(n, gridDim.x, blockIdx.x, s, e);
+    const double hp = vprev ? *hprev : 0.0;
+    double a[1] = {0.0};
+    int64_t i = s + 2 * threadIdx.x;
+    for (; i + 2 * TPB + 1 < e; i += 4 * TPB) {
+        cgs_d2 ta = *reinterpret_cast<const cgs_d2 *>(w + i);
+        cgs_d2 tb = *reinterpret_cast<const cgs_d2 *>(w + i + 2 * TPB);
+        cgs_d2 pa = {0.0, 0.0}, pb = {0.0, 0.0}, va = {0.0, 0.0}, vb = {0.0, 0.0};
+        if (vprev) {
+            pa = *reinterpret_cast<const cgs_d2 *>(vprev + i);
+            pb = *reinterpret_cast<const cgs_d2 *>(vprev + i + 2 * TPB);
+        }
+        if (vj) {
+            va = *reinterpret_cast<const cgs_d2 *>(vj + i);
+            vb = *reinterpret_cast<const cgs_d2 *>(vj + i + 2 * TPB);
+        }
+        if (vprev) {
+            ta.x -= hp * pa.x;
+            ta.y -= hp * pa.y;
+            tb.x -= hp * pb.x;
+            tb.y -= hp * pb.y;
+            *reinterpret_cast<cgs_d2 *>(w + i) = ta;
+            *reinterpret_cast<cgs_d2 *>(w + i + 2 * TPB) = tb;
+        }
+        if (!vj) {
+            va = ta;
+            vb = tb;
+        }
+        a[0] += va.x * ta.x;
+        a[0] += va.y * ta.y;
+        a[0] += vb.x * tb.x;
+        a[0] += vb.y * tb.y;
+    }
+    for (; i + 1 < e; i += 2 * TPB) {
+        cgs_d2 t = *reinterpret_cast<const cgs_d2 *>(w + i);
+        cgs_d2 v = {0.0, 0.0};
+        if (vj) v = *reinterpret_cast<const cgs_d2 *>(vj + i);
+        if (vprev) {
+            const cgs_d2 p = *reinterpret_cast<const cgs_d2 *>(vprev + i);
+            t.x -= hp * p.x;
+            t.y -= hp * p.y;
+            *reinterpret_cast<cgs_d2 *>(w + i) = t;
+        }
+        if (!vj) v = t;
+        a[0] += v.x * t.x;
+        a[0] += v.y * t.y;
+    }
+    if (((e - s) & 1) && threadIdx.x == 0) {
+        const int64_t l = e - 1;
+        double t = w[l];
+        if (vprev) {
+            t -= hp * vprev[l];
+            w[l] = t;
+        }
+        a[0] += (vj ? vj[l] : t) * t;
+    }
+    a[0] = block_sum(a[0], lds);
+    if (!ticket) {
+        if (threadIdx.x == 0) partial[blockIdx.x] = a[0];
+        return;
+    }
+    double tot[1];
+    if (!ticket_totals<1>(a, partial, lds, ticket, tot)) return;
+    if (threadIdx.x == 0) {
+        *out = tot[0];
+        ticket_reset(ticket);
+    }
+}
+void launch_mgs_step(int64_t n, const double *vprev, const double *hprev, const double *vj, double *w, double *partial,
+                     double *out, unsigned *ticket, hipStream_t st) {
+    k_mgs_step<<<reduce_blocks(n), TPB, 0, st>>>(n, vprev, hprev, vj, w, partial, out, ticket);
 }
 
 __global__ __launch_bounds__(TPB) void k_lincomb(int64_t n, int k, const double *__restrict__ V, int64_t ldv,

@@ -139,6 +139,11 @@ void launch_norm2(int64_t n, const double *x, double *partial, double *out, hipS
 // w -= sum_j h[j] * V[:, j] (h on device, j < k); out = ||w||_2^2 (local) when out != null
 void launch_maxpy_norm(int64_t n, int k, const double *V, int64_t ldv, const double *h_dev,
                        double hscale, double *w, double *partial, double *out, hipStream_t st);
+// one modified Gram-Schmidt step: w -= (*hprev) vprev (vprev != null), then (w, vj) over the
+// updated w, (w, w) when vj is null.  ticket != null: the last block to arrive writes the sum
+// to *out (a zeroed ticket word; one launch); else partial[block] (launch_final follows)
+void launch_mgs_step(int64_t n, const double *vprev, const double *hprev, const double *vj, double *w, double *partial,
+                     double *out, unsigned *ticket, hipStream_t st);
 // y = sum_j c[j] * V[:, j] (c on device)
 void launch_lincomb(int64_t n, int k, const double *V, int64_t ldv, const double *c_dev, double *y,
                     hipStream_t st);

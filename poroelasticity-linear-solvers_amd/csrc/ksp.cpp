@@ -86,8 +86,12 @@ void KSP::ensure_work(Ctx &c) {
             if (type == "fgmres") Z.alloc((size_t)restart * ldv);
             else t1.alloc(n);
             t2.alloc(n);
-            dh.alloc(restart + 4);
+            dh.alloc(2 * restart + 4);  // two CGS passes of restart + 1 scalars each
             allocated_k = restart;
+        }
+        if (orthog == MGS && !mgs_part.p) {
+            mgs_part.alloc(reduce_blocks(n));
+            mgs_ticket.alloc(1);
         }
         return;
     }
@@ -172,10 +176,11 @@ void KSP::solve_gmres(const double *b, double *x, Ctx &c) {
     const int64_t mk = restart;
     const double haptol = 1e-30;
     std::vector<double> HH((mk + 1) * (mk + 1), 0.0), cc(mk + 1, 0.0), ss(mk + 1, 0.0), grs(mk + 2, 0.0),
-        nrs(mk + 1, 0.0);
+        nrs(mk + 1, 0.0), hcol(mk + 1, 0.0);
     auto H = [&](int64_t i, int64_t j) -> double & { return HH[(size_t)i * (mk + 1) + j]; };
     double *t1p = t1.p, *t2p = t2.p;  // (no t1 for fgmres: right, with the PC's output in Z)
     launch_set(n, 0.0, x, c.st);
+    if (orthog == MGS) HIPCHK(hipMemsetAsync(mgs_ticket.p, 0, sizeof(unsigned), c.st));
     its = 0;
     reason = 0;
     bool first = true;
@@ -211,15 +216,8 @@ void KSP::solve_gmres(const double *b, double *x, Ctx &c) {
                 pc->apply(t1p, vn, c);
             }
             const int k = (int)(loc_it + 1);
-            launch_mdot(n, k, nullptr, V.p, ldv, vn, c.partials(n, k), dh.p, c.st);
-            c.comm->global_sum_dev(dh.p, k, c.st);
-            launch_maxpy_norm(n, k, V.p, ldv, dh.p, -1.0, vn, c.partials(n, 1), dh.p + k, c.st);
-            c.comm->global_sum_dev(dh.p + k, 1, c.st);
-            double *hs = c.host_scalars(k + 1);
-            HIPCHK(hipMemcpyAsync(hs, dh.p, sizeof(double) * (k + 1), hipMemcpyDeviceToHost, c.st));
-            c.sync();
-            for (int j = 0; j < k; ++j) H(j, loc_it) = hs[j];
-            const double tt = std::sqrt(hs[k]);
+            const double tt = std::sqrt(gmres_orthogonalise(k, vn, hcol.data(), c));
+            for (int j = 0; j < k; ++j) H(j, loc_it) = hcol[j];
             H(loc_it + 1, loc_it) = tt;
             double hapbnd = std::fabs(tt / grs[loc_it]);
             if (hapbnd > haptol) hapbnd = haptol;
@@ -284,6 +282,65 @@ void KSP::solve_gmres(const double *b, double *x, Ctx &c) {
         }
         first = false;
     }
+}
+
+// The orthogonalisation of one Arnoldi step (PETSc's gborthog.c rules), w = column k of V:
+//   CGS            h = V^T w, w -= V h in one multi-vector kernel each (refine_never);
+//                  refine_always runs the pair again on the updated w and adds the second
+//                  pass's l_j to h_j here, in double; refine_ifneeded does so exactly when
+//                  ||w|| after the first pass is smaller than sqrt(sum_j h_j^2) (j ascending)
+//   MGS            for j ascending: h_j = (w, v_j), w -= h_j v_j -- k dependent reductions,
+//                  so k + 1 launches of one step kernel (the update by h_{j-1} fused into the
+//                  launch that sums (w, v_j); the last one sums (w, w)), each reading its
+//                  coefficient from dh, where the launch before it left it.  k_final and the
+//                  global sum sit between the steps; with pls.gmres_mgs_fused, on one rank, the
+//                  last block to arrive finishes each sum in its launch instead (not the
+//                  default: 4 % slower at 10M rows, a tie at 2,669).  The
+//                  same order of summation either way: bitwise the same on one rank.
+// The k + 1 scalars come to the host in one read-back per pass.
+double KSP::gmres_orthogonalise(int k, double *w, double *h, Ctx &c) {
+    double *hs = c.host_scalars(k + 1);
+    auto read_back = [&](const double *d) {
+        HIPCHK(hipMemcpyAsync(hs, d, sizeof(double) * (k + 1), hipMemcpyDeviceToHost, c.st));
+        c.sync();
+    };
+    ++stat_orth_steps;
+    if (orthog == MGS) {
+        const bool fuse = mgs_fused && c.comm->size == 1;
+        for (int j = 0; j <= k; ++j) {
+            launch_mgs_step(n, j > 0 ? V.p + (int64_t)(j - 1) * ldv : nullptr, j > 0 ? dh.p + (j - 1) : nullptr,
+                            j < k ? V.p + (int64_t)j * ldv : nullptr, w, mgs_part.p, dh.p + j,
+                            fuse ? mgs_ticket.p : nullptr, c.st);
+            if (!fuse) {
+                launch_final(n, 1, mgs_part.p, dh.p + j, c.st);
+                c.comm->global_sum_dev(dh.p + j, 1, c.st);
+            }
+        }
+        read_back(dh.p);
+        std::copy(hs, hs + k, h);
+        return hs[k];
+    }
+    auto cgs_pass = [&](double *d) {
+        launch_mdot(n, k, nullptr, V.p, ldv, w, c.partials(n, k), d, c.st);
+        c.comm->global_sum_dev(d, k, c.st);
+        launch_maxpy_norm(n, k, V.p, ldv, d, -1.0, w, c.partials(n, 1), d + k, c.st);
+        c.comm->global_sum_dev(d + k, 1, c.st);
+        read_back(d);
+    };
+    cgs_pass(dh.p);
+    std::copy(hs, hs + k, h);
+    bool again = orthog == CGS_ALWAYS;
+    if (orthog == CGS_IFNEEDED) {
+        double hh = 0.0;
+        for (int j = 0; j < k; ++j) hh += h[j] * h[j];
+        again = std::sqrt(hs[k]) < std::sqrt(hh);
+    }
+    if (again) {
+        ++stat_orth_second;
+        cgs_pass(dh.p + k + 1);
+        for (int j = 0; j < k; ++j) h[j] += hs[j];
+    }
+    return hs[k];
 }
 
 // ----------------------------------------------- the device-resident loops --
@@ -646,8 +703,17 @@ std::unique_ptr<KSP> make_ksp(const std::string &prefix, const Options &o, const
     if (prefix == "global_") k->time_limit = o.num("pls.solver_time_limit", 0.0);
     k->bcgs_device = o.flag("pls.bcgs_device", true);
     k->bcgs_fused = o.flag("pls.bcgs_fused_reduce", true);
-    if (o.has(prefix + "ksp_gmres_modifiedgramschmidt") && (k->type == "gmres" || k->type == "fgmres"))
-        throw Error(prefix + "ksp_gmres_modifiedgramschmidt: only classical Gram-Schmidt is implemented");
+    if (k->type == "gmres" || k->type == "fgmres") {
+        // KSPSetFromOptions_GMRES reads the classical flag first, so the modified one wins when both
+        // are given; the refinement type is CGS's alone (other types ignore all three options)
+        const std::string key = prefix + "ksp_gmres_cgs_refinement_type", rt = o.str(key, "refine_never");
+        if (rt == "refine_never") k->orthog = KSP::CGS_NEVER;
+        else if (rt == "refine_ifneeded") k->orthog = KSP::CGS_IFNEEDED;
+        else if (rt == "refine_always") k->orthog = KSP::CGS_ALWAYS;
+        else throw Error(key + ": unknown value '" + rt + "' (refine_never, refine_ifneeded, refine_always)");
+        if (o.flag(prefix + "ksp_gmres_modifiedgramschmidt", false)) k->orthog = KSP::MGS;
+        k->mgs_fused = o.flag("pls.gmres_mgs_fused", false);
+    }
     k->resolve_side_norm(o.str(prefix + "ksp_pc_side", ""), o.str(prefix + "ksp_norm_type", ""));
     if (Amat) {
         k->owned_op = std::make_unique<MatOp>(Amat);

@@ -557,7 +557,14 @@ struct KSP {
     DBuf<unsigned> bcticket;  // ... the tickets of its single-launch reductions
     bool bcgs_device = true;  // pls.bcgs_device: BiCGStab's recurrence on the device
     bool bcgs_fused = true;   // pls.bcgs_fused_reduce: the last block to arrive finishes each sum (one rank only)
-    DBuf<double> dh;  // device Hessenberg column / coefficients
+    DBuf<double> dh;  // device Hessenberg column / coefficients (and a second CGS pass's column behind it)
+    // GMRES orthogonalisation (gmres, fgmres): ksp_gmres_modifiedgramschmidt, ksp_gmres_cgs_refinement_type
+    enum Orthog { CGS_NEVER = 0, CGS_IFNEEDED = 1, CGS_ALWAYS = 2, MGS = 3 };
+    int orthog = CGS_NEVER;
+    bool mgs_fused = false;      // pls.gmres_mgs_fused: the last block to arrive finishes each MGS sum (one rank only)
+    DBuf<double> mgs_part;       // MGS: one row of partials ...
+    DBuf<unsigned> mgs_ticket;   // ... and the ticket of its single-launch reductions
+    int64_t stat_orth_steps = 0, stat_orth_second = 0;  // Arnoldi steps orthogonalised, second CGS passes
     DBuf<double> cgS, cghist;  // device-resident CG: scalar state, residual history
     DBuf<int64_t> cgI;
     bool cg_device = true;     // pls.cg_device: CG's recurrences on the device (no read-back per iteration)
@@ -577,6 +584,9 @@ struct KSP {
   private:
     void ensure_work(Ctx &c);
     void solve_gmres(const double *b, double *x, Ctx &c);  // gmres and fgmres
+    // one Arnoldi step: w orthogonalised against the first k columns of V; the Hessenberg
+    // column's k entries into h (host), ||w||^2 returned
+    double gmres_orthogonalise(int k, double *w, double *h, Ctx &c);
     void solve_cg(const double *b, double *x, Ctx &c);
     void solve_cg_dev(const double *b, double *x, Ctx &c);
     void solve_bcgs(const double *b, double *x, Ctx &c);

@@ -226,6 +226,14 @@ class Handle:
         N.check(N.lib().pls_get_ksp_stats(self.ptr, prefix.encode(), N.ptr(s)))
         return tuple(int(v) for v in s)
 
+    def gmres_orthog_stats(self, prefix):
+        """(Arnoldi steps orthogonalised, second classical Gram-Schmidt passes, scheme: 0 CGS
+        refine_never, 1 refine_ifneeded, 2 refine_always, 3 modified Gram-Schmidt) of the gmres /
+        fgmres solver with this options prefix (pls_get_gmres_orthog_stats)."""
+        s = np.zeros(3, dtype=np.int64)
+        N.check(N.lib().pls_get_gmres_orthog_stats(self.ptr, prefix.encode(), N.ptr(s)))
+        return tuple(int(v) for v in s)
+
     def reset_timings(self):
         N.check(N.lib().pls_reset_timings(self.ptr))
 
