@@ -217,6 +217,18 @@ int pls_get_ksp_stats(pls_handle *h, const char *prefix, int64_t stats[5]);
  * 2 refine_always, 3 modified Gram-Schmidt).  An unknown prefix or a KSP of
  * another type is an error.                                                 */
 int pls_get_gmres_orthog_stats(pls_handle *h, const char *prefix, int64_t stats[3]);
+/* The eigenvalue bounds of the chebyshev KSP with this prefix: out[0] emin and
+ * [1] emax as used, [2] the smallest and [3] the largest real part of the
+ * estimate's Hessenberg eigenvalues (NaN when the bounds were given with
+ * <prefix>ksp_chebyshev_eigenvalues).  An unknown prefix, a KSP of another type
+ * or one that has not run a solve since it was set up is an error.           */
+int pls_get_chebyshev_bounds(pls_handle *h, const char *prefix, double out[4]);
+/* Eigenvalues of the leading m x m part (1 <= m <= 64) of an upper Hessenberg
+ * matrix stored by columns, H[i + j * ldh]; entries below the subdiagonal are
+ * not read.  Host code (shifted QR, no LAPACK, no device): re[k] + i im[k], in
+ * no particular order.  Returns nonzero when the iteration does not converge
+ * or an argument is out of range (no error message is set).                  */
+int pls_hessenberg_eigenvalues(int m, const double *H, int ldh, double *re, double *im);
 
 /* Export a device matrix of the handle to host CSR (tests / parity):
  * which: 0 = A, 1 = P, 2 = P_diff (field-major order).  Call once with

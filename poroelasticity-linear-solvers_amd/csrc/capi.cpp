@@ -1745,6 +1745,24 @@ int pls_get_gmres_orthog_stats(pls_handle *hh, const char *prefix, int64_t *stat
         stats[2] = found->orthog;
     })
 }
+int pls_get_chebyshev_bounds(pls_handle *hh, const char *prefix, double *out) {
+    PLS_TRY({
+        const KSP *found = find_ksp(*reinterpret_cast<Handle *>(hh), prefix, out, "pls_get_chebyshev_bounds");
+        if (found->type != "chebyshev")
+            throw Error("pls_get_chebyshev_bounds: the solver with prefix '" + found->prefix + "' is of type " +
+                        found->type + ", not chebyshev");
+        if (!found->stat_solves || !found->cheb_ready)
+            throw Error("pls_get_chebyshev_bounds: the solver with prefix '" + found->prefix +
+                        "' has not run a solve yet");
+        out[0] = found->cheb_emin;
+        out[1] = found->cheb_emax;
+        out[2] = found->cheb_raw[0];
+        out[3] = found->cheb_raw[1];
+    })
+}
+int pls_hessenberg_eigenvalues(int m, const double *H, int ldh, double *re, double *im) {
+    return hessenberg_eigenvalues(m, H, ldh, re, im);
+}
 int pls_reset_timings(pls_handle *hh) { PLS_TRY(reinterpret_cast<Handle *>(hh)->timers.reset()) }
 
 int pls_export_matrix(pls_handle *hh, int which, int64_t *nrows, int64_t *nnz, int64_t *row_ptr, int32_t *col,
@@ -1919,6 +1937,8 @@ int pls_update_matrices(pls_handle *hh, const pls_csr *A, const pls_csr *P, cons
             H.have_Pd = true;
         }
         H.setup_done = false;
+        // (the inner solvers are built again by the setup; the outer one persists)
+        if (H.outer && !H.outer->cheb_explicit) H.outer->cheb_ready = false;
     })
 }
 

@@ -551,6 +551,23 @@ __global__ __launch_bounds__(TPB) void k_cheb_step(int64_t n, const double *__re
     }
 }
 
+// Polynomial KSP update (richardson, chebyshev; ksp.cpp): out = a pm1 + b pk + c t with
+// t = dinv . z (the Jacobi PC fused in) or t = z.  A null pm1 / pk term is omitted, not
+// multiplied by zero; out may alias pm1 or pk (every entry is read before it is written,
+// by the thread that writes it).  One body for the first step (c t), Richardson's
+// x += scale z and the three-term step: t is a rounded product, then one fma per term.
+__global__ __launch_bounds__(TPB) void k_poly_update(int64_t n, double a, const double *pm1, double b,
+                                                     const double *pk, double c, const double *dinv,
+                                                     const double *z, double *out) {
+    for (int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x; i < n; i += (int64_t)gridDim.x * TPB) {
+        const double t = dinv ? dinv[i] * z[i] : z[i];
+        double v = c * t;
+        if (pk) v = fma(b, pk[i], v);
+        if (pm1) v = fma(a, pm1[i], v);
+        out[i] = v;
+    }
+}
+
 static inline unsigned stream_grid(int64_t n) {
     int64_t g = (n + TPB - 1) / TPB;
     if (g > 8192) g = 8192;
@@ -674,6 +691,10 @@ void launch_pointwise_mult(int64_t n, const double *x, const double *d, double *
 void launch_cheb_step(int64_t n, const double *dinv, const double *r, double *d, double *x, double a, double bc,
                       int flags, hipStream_t st) {
     if (n > 0) k_cheb_step<<<stream_grid(n), TPB, 0, st>>>(n, dinv, r, d, x, a, bc, flags);
+}
+void launch_poly_update(int64_t n, double a, const double *pm1, double b, const double *pk, double c,
+                        const double *dinv, const double *z, double *out, hipStream_t st) {
+    if (n > 0) k_poly_update<<<stream_grid(n), TPB, 0, st>>>(n, a, pm1, b, pk, c, dinv, z, out);
 }
 void launch_zero_entries(int64_t m, const int32_t *idx, double *y, hipStream_t st) {
     if (m > 0) k_zero_entries<<<grid_for(m, TPB), TPB, 0, st>>>(m, idx, y);

@@ -123,6 +123,10 @@ void launch_pointwise_mult(int64_t n, const double *x, const double *d, double *
 // (d = bc (dinv . r)); flags 2: x not read (x = d)
 void launch_cheb_step(int64_t n, const double *dinv, const double *r, double *d, double *x, double a, double bc,
                       int flags, hipStream_t st);
+// polynomial KSP update: out = a pm1 + b pk + c t, t = dinv ? dinv . z : z; a null pm1 / pk
+// term is omitted; out may alias pm1 or pk
+void launch_poly_update(int64_t n, double a, const double *pm1, double b, const double *pk, double c,
+                        const double *dinv, const double *z, double *out, hipStream_t st);
 void launch_zero_entries(int64_t m, const int32_t *idx, double *y, hipStream_t st);
 void launch_gather(int64_t n, const int64_t *idx, const double *x, double *y, hipStream_t st);
 void launch_scatter(int64_t n, const int64_t *idx, const double *x, double *y, hipStream_t st);

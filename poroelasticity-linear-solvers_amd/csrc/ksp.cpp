@@ -1,12 +1,15 @@
 // ksp.cpp -- the PETSc-semantics Krylov solvers of libpls.so (declared in
-// runtime.hpp): GMRES / FGMRES, CG, BiCGStab, PREONLY and KSPConvergedDefault.
+// runtime.hpp): GMRES / FGMRES, CG, BiCGStab, Richardson, Chebyshev, PREONLY and
+// KSPConvergedDefault.
 //
 // The algorithms follow PETSc as the reference configures it (reference
 // lib/Solver.py:91-102 for the outer solver, lib/Preconditioner.py:94-118 for
 // the inner ones): GMRES with classical Gram-Schmidt, Givens rotations,
 // happy-breakdown test and BuildSoln (gmres.c, fgmres.c); CG (cg.c); BiCGStab
-// (bcgs.c); KSPConvergedDefault (iterativ.c).  GMRES's scalar recurrences run
-// on the host in double precision, as the CPU oracle evaluates them; CG's and
+// (bcgs.c); Richardson (rich.c) and Chebyshev (cheby.c) without inner products
+// when the norm type is none; KSPConvergedDefault (iterativ.c).  GMRES's
+// scalar recurrences run on the host in double precision, as the CPU oracle
+// evaluates them (Richardson and Chebyshev have none beyond a norm); CG's and
 // BiCGStab's run on the device unless something needs each iteration on the
 // host (KSP::device_loop_allowed).
 #include "runtime.hpp"
@@ -62,7 +65,18 @@ void KSP::resolve_side_norm(const std::string &side, const std::string &nt) {
             throw Error("KSPCG (" + prefix + "): unsupported norm type " + norm);
         return;
     }
-    throw Error("KSP type '" + type + "' (prefix " + prefix + ") is not available (supported: gmres, fgmres, cg, bcgs, preonly)");
+    if (type == "richardson" || type == "chebyshev") {
+        const std::string who = type == "chebyshev" ? "KSPCHEBYSHEV" : "KSPRICHARDSON";
+        if (!side.empty() && side != "left")
+            throw Error(who + " (" + prefix + ") supports only left preconditioning, not pc side " + side);
+        right = false;
+        norm = nt.empty() ? "preconditioned" : nt;
+        if (norm != "preconditioned" && norm != "unpreconditioned" && norm != "none")
+            throw Error(who + " (" + prefix + "): unsupported norm type " + norm);
+        return;
+    }
+    throw Error("KSP type '" + type + "' (prefix " + prefix +
+                ") is not available (supported: gmres, fgmres, cg, bcgs, preonly, richardson, chebyshev)");
 }
 
 // May this solve (CG or BiCGStab) run its recurrence on the device?  Not when
@@ -92,6 +106,15 @@ void KSP::ensure_work(Ctx &c) {
         if (orthog == MGS && !mgs_part.p) {
             mgs_part.alloc(reduce_blocks(n));
             mgs_ticket.alloc(1);
+        }
+        return;
+    }
+    if (type == "richardson" || type == "chebyshev") {
+        if (allocated_k != -2) {
+            t1.alloc(n);  // r
+            t2.alloc(n);  // z
+            if (type == "chebyshev") t3.alloc(n);  // the iterate that is not in x
+            allocated_k = -2;
         }
         return;
     }
@@ -146,6 +169,8 @@ void KSP::solve(const double *b, double *x, Ctx &c) {
     } else {
         ensure_work(c);
         if (type == "gmres" || type == "fgmres") solve_gmres(b, x, c);
+        else if (type == "richardson") solve_richardson(b, x, c);
+        else if (type == "chebyshev") solve_chebyshev(b, x, c);
         else if (type == "cg") device_loop_allowed() ? solve_cg_dev(b, x, c) : solve_cg(b, x, c);
         else device_loop_allowed() ? solve_bcgs_dev(b, x, c) : solve_bcgs(b, x, c);  // bcgs: no other type is left
     }
@@ -179,6 +204,7 @@ void KSP::solve_gmres(const double *b, double *x, Ctx &c) {
         nrs(mk + 1, 0.0), hcol(mk + 1, 0.0);
     auto H = [&](int64_t i, int64_t j) -> double & { return HH[(size_t)i * (mk + 1) + j]; };
     double *t1p = t1.p, *t2p = t2.p;  // (no t1 for fgmres: right, with the PC's output in Z)
+    if (keep_hess) hess.assign((size_t)(mk + 1) * (mk + 1), 0.0);
     launch_set(n, 0.0, x, c.st);
     if (orthog == MGS) HIPCHK(hipMemsetAsync(mgs_ticket.p, 0, sizeof(unsigned), c.st));
     its = 0;
@@ -219,6 +245,10 @@ void KSP::solve_gmres(const double *b, double *x, Ctx &c) {
             const double tt = std::sqrt(gmres_orthogonalise(k, vn, hcol.data(), c));
             for (int j = 0; j < k; ++j) H(j, loc_it) = hcol[j];
             H(loc_it + 1, loc_it) = tt;
+            if (keep_hess && first) {
+                for (int j = 0; j < k; ++j) hess[(size_t)j + (size_t)loc_it * (mk + 1)] = hcol[j];
+                hess[(size_t)k + (size_t)loc_it * (mk + 1)] = tt;
+            }
             double hapbnd = std::fabs(tt / grs[loc_it]);
             if (hapbnd > haptol) hapbnd = haptol;
             const bool hapend = tt < hapbnd;
@@ -686,6 +716,206 @@ void KSP::solve_bcgs_dev(const double *b, double *x, Ctx &c) {
     bcgs_end(x, c);
 }
 
+// --------------------------------------------------- Richardson, Chebyshev --
+// KSPSolve_Richardson (no self-scaling) and KSPSolve_Chebyshev (first kind),
+// left preconditioning, zero initial guess.  Neither takes an inner product:
+// with norm type none the whole solve is enqueued without a read-back or a
+// synchronisation and applies the same linear operator every time, so it is a
+// legal preconditioner for plain GMRES.  With a norm the host loop reads one
+// scalar back per iteration, as GMRES does.  Work vectors: r t1, z t2 and
+// (Chebyshev) the iterate that is not in x, t3.  Every vector update is one
+// launch of k_poly_update; over PCJacobi (and no preconditioned norm to form
+// z = B r for) the PC's product happens in that launch too: two launches per
+// iteration, the residual product and the update.
+const double *KSP::poly_dinv() const {
+    if (!poly_fuse_jacobi || norm == "preconditioned") return nullptr;
+    const PCJacobi *j = dynamic_cast<const PCJacobi *>(pc);
+    return j ? j->dinv.p : nullptr;
+}
+
+// rn(r): ||B r|| (z = B r is left in z) or ||r||
+double KSP::poly_norm(const double *r, double *z, Ctx &c) {
+    if (norm == "preconditioned") {
+        pc->apply(r, z, c);
+        return c.norm2(n, z);
+    }
+    return c.norm2(n, r);
+}
+
+void KSP::poly_step(double a, const double *pm1, double b, const double *pk, double cz, const double *r, double *z,
+                    bool z_done, double *out, Ctx &c) {
+    if (const double *dinv = poly_dinv()) {
+        launch_poly_update(n, a, pm1, b, pk, cz, dinv, r, out, c.st);
+        return;
+    }
+    if (!z_done) pc->apply(r, z, c);
+    launch_poly_update(n, a, pm1, b, pk, cz, nullptr, z, out, c.st);
+}
+
+void KSP::solve_richardson(const double *b, double *x, Ctx &c) {
+    const bool normed = norm != "none", pnorm = norm == "preconditioned";
+    double *rw = t1.p, *z = t2.p;
+    const double *r = b;
+    its = 0;
+    reason = 0;
+    rnorm = 0.0;
+    for (int64_t i = 0; i < maxit; ++i) {
+        if (normed) {
+            reason = record((int)i, poly_norm(r, z, c));
+            if (reason) break;
+        }
+        // x = 0 is never written: the first update omits the x term
+        poly_step(0.0, nullptr, 1.0, i > 0 ? x : nullptr, rich_scale, r, z, pnorm, x, c);
+        its++;
+        if (i + 1 < maxit || normed) {
+            A->residual(x, b, rw, c);
+            r = rw;
+        }
+    }
+    if (its == 0) launch_set(n, 0.0, x, c.st);
+    if (reason) return;
+    if (!normed) {
+        reason = CONVERGED_ITS;
+        return;
+    }
+    reason = record((int)std::max<int64_t>(maxit, 0), poly_norm(r, z, c));
+    if (!reason) reason = DIVERGED_ITS;
+}
+
+void KSP::solve_chebyshev(const double *b, double *x, Ctx &c) {
+    if (!cheb_ready) chebyshev_estimate(c);
+    const bool normed = norm != "none", pnorm = norm == "preconditioned";
+    const double scale = 2.0 / (cheb_emax + cheb_emin), alpha = 1.0 - scale * cheb_emin, mu = 1.0 / alpha,
+                 omegaprod = 2.0 / alpha;
+    double c_km1 = 1.0, c_k = mu;
+    double *rw = t1.p, *z = t2.p;
+    its = 0;
+    reason = 0;
+    rnorm = 0.0;
+    if (normed) reason = record(0, poly_norm(b, z, c));
+    if (!reason && maxit <= 0) reason = DIVERGED_ITS;
+    if (reason) {
+        launch_set(n, 0.0, x, c.st);
+        return;
+    }
+    // two buffers take the iterates in turn (p_k+1 overwrites p_k-1); the one that update
+    // maxit - 1, the last, writes is x, so a solve that runs to max_it ends without a copy
+    auto buf = [&](int64_t j) { return (maxit - 1 - j) % 2 == 0 ? x : t3.p; };
+    const double *pkm1 = nullptr;
+    double *pk = buf(0);
+    poly_step(0.0, nullptr, 0.0, nullptr, scale, b, z, pnorm, pk, c);
+    its = 1;
+    int64_t i = 1;
+    for (; i < maxit; ++i) {
+        its++;
+        const double c_kp1 = 2.0 * mu * c_k - c_km1, omega = omegaprod * c_k / c_kp1;
+        A->residual(pk, b, rw, c);
+        if (normed) {
+            reason = record((int)i, poly_norm(rw, z, c));
+            if (reason) break;
+        }
+        double *out = buf(i);  // (i == 1: p_k-1 = 0, its term omitted)
+        poly_step(1.0 - omega, pkm1, omega, pk, omega * scale, rw, z, pnorm, out, c);
+        pkm1 = pk;
+        pk = out;
+        c_km1 = c_k;
+        c_k = c_kp1;
+    }
+    if (!reason) {
+        if (!normed) {
+            reason = CONVERGED_ITS;
+        } else {
+            A->residual(pk, b, rw, c);
+            reason = record((int)i, poly_norm(rw, z, c));
+            if (!reason) reason = DIVERGED_ITS;
+        }
+    }
+    if (pk != x) launch_copy(n, pk, x, c.st);
+}
+
+// PETSc's default bounds: cheb_steps Arnoldi steps of the left-preconditioned operator B A
+// through the GMRES cycle of a child KSP (CGS, no refinement, no tolerance), the extreme real
+// parts of the Hessenberg matrix's eigenvalues, transformed by ksp_chebyshev_esteig a,b,c,d.
+// The right-hand side is a fixed function of the block-global row index (PETSc's is random):
+// v_g = ((g + 1) * 2654435761 mod 2^32) / 2^32 - 0.5, the same vector on every rank count.
+void KSP::chebyshev_estimate(Ctx &c) {
+    const std::string who = "KSPCHEBYSHEV (" + prefix + "): ";
+    const std::string ask = "; give " + prefix + "ksp_chebyshev_eigenvalues emin,emax";
+    const MatOp *mo = dynamic_cast<const MatOp *>(A);
+    if (!mo)
+        throw Error(who + "the eigenvalue estimate needs the block-global row indices of an assembled operator, this one is matrix-free" + ask);
+    const DevCSR &M = *mo->M;
+    const Halo *halo = M.halo.get();
+    if (halo && (halo->nlocal != n || (int64_t)halo->l2g.size() < n))
+        throw Error(who + "the eigenvalue estimate needs the block-global row indices, this distributed operator has none" + ask);
+    std::vector<double> v(n);
+    for (int64_t i = 0; i < n; ++i) {
+        const uint64_t g = (uint64_t)(halo ? halo->l2g[i] : i);
+        v[i] = (double)(((g + 1) * 2654435761ull) & 0xffffffffull) / 4294967296.0 - 0.5;
+    }
+    DBuf<double> rhs(std::max<int64_t>(n, 1)), sol(std::max<int64_t>(n, 1));
+    launch_set(n, 1.0, rhs.p, c.st);
+    const int64_t nglob = (int64_t)std::llround(c.dot(n, rhs.p, rhs.p));  // rows of the whole block
+    if (n) HIPCHK(hipMemcpyAsync(rhs.p, v.data(), sizeof(double) * n, hipMemcpyHostToDevice, c.st));
+    c.sync();
+    const int64_t steps = std::min<int64_t>(cheb_steps, nglob);
+    if (steps < 1) throw Error(who + "empty operator");
+    if (!cheb_est) {
+        cheb_est = std::make_unique<KSP>();
+        KSP &k = *cheb_est;
+        k.prefix = prefix + "esteig_";
+        k.type = "gmres";
+        k.right = false;
+        k.norm = "preconditioned";
+        k.orthog = CGS_NEVER;
+        k.rtol = k.atol = 0.0;
+        k.dtol = INFINITY;
+        k.keep_hess = true;
+        k.A = A;
+        k.pc = pc;
+        k.n = n;
+    }
+    KSP &k = *cheb_est;
+    k.maxit = k.restart = steps;
+    k.solve(rhs.p, sol.p, c);
+    c.sync();
+    const int m = k.its;
+    double re[64], im[64];
+    if (m < 1) throw Error(who + "the eigenvalue estimate made no Arnoldi step" + ask);
+    if (hessenberg_eigenvalues(m, k.hess.data(), (int)(steps + 1), re, im))
+        throw Error(who + "the Hessenberg eigenvalue iteration of the estimate did not converge" + ask);
+    const double lo = *std::min_element(re, re + m), hi = *std::max_element(re, re + m);
+    const double emin = cheb_tr[0] * lo + cheb_tr[1] * hi, emax = cheb_tr[2] * lo + cheb_tr[3] * hi;
+    if (!(emin > 0.0 && emin < emax))
+        throw Error(who + "estimated bounds " + std::to_string(emin) + ", " + std::to_string(emax) +
+                    " are not 0 < emin < emax" + ask);
+    cheb_raw[0] = lo;
+    cheb_raw[1] = hi;
+    cheb_emin = emin;
+    cheb_emax = emax;
+    cheb_ready = true;
+}
+
+namespace {
+std::vector<double> comma_list(const std::string &text, const std::string &key) {
+    std::vector<double> v;
+    size_t a = 0;
+    while (a <= text.size()) {
+        const size_t b = std::min(text.find(',', a), text.size());
+        try {
+            size_t used = 0;
+            const std::string tok = text.substr(a, b - a);
+            v.push_back(std::stod(tok, &used));
+            if (used != tok.size()) throw 0;
+        } catch (...) {
+            throw Error("option " + key + ": not a comma-separated list of numbers: " + text);
+        }
+        a = b + 1;
+    }
+    return v;
+}
+}  // namespace
+
 std::unique_ptr<KSP> make_ksp(const std::string &prefix, const Options &o, const DevCSR *Amat, const DevCSR *Pmat,
                               const std::string &default_ksp, const std::string &default_pc, Ctx &c, double rtol,
                               double atol, double dtol, int64_t maxit, int64_t restart, PC *external_pc) {
@@ -715,6 +945,35 @@ std::unique_ptr<KSP> make_ksp(const std::string &prefix, const Options &o, const
         k->mgs_fused = o.flag("pls.gmres_mgs_fused", false);
     }
     k->resolve_side_norm(o.str(prefix + "ksp_pc_side", ""), o.str(prefix + "ksp_norm_type", ""));
+    k->poly_fuse_jacobi = o.flag("pls.poly_fuse_jacobi", true);
+    if (k->type == "richardson") {
+        if (o.has(prefix + "ksp_richardson_self_scale"))
+            throw Error("KSPRICHARDSON (" + prefix + "): ksp_richardson_self_scale is not available");
+        k->rich_scale = o.num(prefix + "ksp_richardson_scale", 1.0);
+    }
+    if (k->type == "chebyshev") {
+        const std::string who = "KSPCHEBYSHEV (" + prefix + "): ";
+        if (o.has(prefix + "ksp_chebyshev_eigenvalues")) {
+            const std::string key = prefix + "ksp_chebyshev_eigenvalues";
+            const std::vector<double> v = comma_list(o.str(key, ""), key);
+            if (v.size() != 2) throw Error(who + key + " takes emin,emax (one token)");
+            if (!(v[0] > 0.0 && v[0] < v[1]))
+                throw Error(who + key + " needs 0 < emin < emax, got " + o.str(key, ""));
+            k->cheb_explicit = k->cheb_ready = true;
+            k->cheb_emin = v[0];
+            k->cheb_emax = v[1];
+            k->cheb_raw[0] = k->cheb_raw[1] = std::nan("");
+        }
+        const std::string tkey = prefix + "ksp_chebyshev_esteig";
+        if (o.has(tkey)) {
+            const std::vector<double> v = comma_list(o.str(tkey, ""), tkey);
+            if (v.size() != 4) throw Error(who + tkey + " takes a,b,c,d (one token)");
+            std::copy(v.begin(), v.end(), k->cheb_tr);
+        }
+        k->cheb_steps = o.integer(prefix + "ksp_chebyshev_esteig_steps", 10);
+        if (k->cheb_steps < 1 || k->cheb_steps > 64)
+            throw Error(who + prefix + "ksp_chebyshev_esteig_steps must be between 1 and 64");
+    }
     if (Amat) {
         k->owned_op = std::make_unique<MatOp>(Amat);
         k->A = k->owned_op.get();

@@ -753,6 +753,17 @@ void MatOp::apply(const double *x, double *y, Ctx &c) {
     if (timers) { timers->end(T_SPMV); timers->spmv_calls++; }
 }
 
+void Op::residual(const double *x, const double *b, double *r, Ctx &c) {
+    apply(x, r, c);
+    launch_waxpby(n, 1.0, b, -1.0, r, r, c.st);
+}
+void MatOp::residual(const double *x, const double *b, double *r, Ctx &c) {
+    if (!M->sell) build_sell(const_cast<DevCSR &>(*M), c);
+    if (timers) timers->begin(T_SPMV);
+    spmv(*M, x, r, c, -1.0, 1.0, b);
+    if (timers) { timers->end(T_SPMV); timers->spmv_calls++; }
+}
+
 // ====================================================== preconditioners ===
 void PCNone::apply(const double *x, double *y, Ctx &c) {
     if (x != y) launch_copy(n, x, y, c.st);

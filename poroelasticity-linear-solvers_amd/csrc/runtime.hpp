@@ -296,6 +296,8 @@ struct Op {
     int64_t n = 0;
     virtual ~Op() = default;
     virtual void apply(const double *x, double *y, Ctx &c) = 0;
+    // r = b - A x (r is neither x nor b); a matrix does it in the product's launch
+    virtual void residual(const double *x, const double *b, double *r, Ctx &c);
 };
 struct MatOp : Op {
     const DevCSR *M;
@@ -303,6 +305,7 @@ struct MatOp : Op {
     explicit MatOp(const DevCSR *m) : M(m) { n = m->nrows; }
     Ctx *ctx_for_build = nullptr;
     void apply(const double *x, double *y, Ctx &c) override;
+    void residual(const double *x, const double *b, double *r, Ctx &c) override;
 };
 
 // --------------------------------------------------------- preconditioners --
@@ -494,6 +497,10 @@ struct PCBandLU : PC {
     int32_t check_fail(Ctx &c);  // synchronising: the fail word (2: a sweep spin gave up)
 };
 // Lower / upper bandwidth of a square CSR matrix with sorted rows.
+// Eigenvalues of the leading m x m of an upper Hessenberg matrix (column-major, H[i + j * ldh];
+// entries below the subdiagonal are not read), m <= 64: shifted QR in complex arithmetic, no
+// LAPACK.  Returns nonzero when it fails to converge (or m is out of range).
+int hessenberg_eigenvalues(int m, const double *H, int ldh, double *re, double *im);
 void csr_bandwidths(const DevCSR &M, int64_t &kl, int64_t &ku, Ctx &c);
 // -pc_type lu / cholesky (MUMPS in the reference): dense inverse up to
 // pls.lu_dense_max rows, else the sparse (nested dissection, multifrontal) LU;
@@ -565,6 +572,20 @@ struct KSP {
     DBuf<double> mgs_part;       // MGS: one row of partials ...
     DBuf<unsigned> mgs_ticket;   // ... and the ticket of its single-launch reductions
     int64_t stat_orth_steps = 0, stat_orth_second = 0;  // Arnoldi steps orthogonalised, second CGS passes
+    // GMRES: keep the Hessenberg columns of the first cycle as Arnoldi made them (the cycle
+    // rotates its own copy in place): hess[i + j * (restart + 1)], column j = step j
+    bool keep_hess = false;
+    std::vector<double> hess;
+    // richardson, chebyshev (left, zero initial guess, no inner products unless a norm is asked for)
+    double rich_scale = 1.0;        // ksp_richardson_scale
+    bool poly_fuse_jacobi = true;   // pls.poly_fuse_jacobi: PCJacobi's product inside the update kernel
+    bool cheb_explicit = false;     // ksp_chebyshev_eigenvalues emin,emax given
+    double cheb_emin = 0.0, cheb_emax = 0.0;  // the bounds in use (cheb_ready)
+    double cheb_raw[2] = {0.0, 0.0};          // the estimate's smallest / largest real part (NaN when explicit)
+    double cheb_tr[4] = {0.0, 0.1, 0.0, 1.1};  // ksp_chebyshev_esteig a,b,c,d
+    int64_t cheb_steps = 10;                   // ksp_chebyshev_esteig_steps
+    bool cheb_ready = false;  // bounds set (explicit: at creation; estimated: at the first solve)
+    std::unique_ptr<KSP> cheb_est;  // the GMRES that runs the estimate's Arnoldi steps
     DBuf<double> cgS, cghist;  // device-resident CG: scalar state, residual history
     DBuf<int64_t> cgI;
     bool cg_device = true;     // pls.cg_device: CG's recurrences on the device (no read-back per iteration)
@@ -591,6 +612,15 @@ struct KSP {
     void solve_cg_dev(const double *b, double *x, Ctx &c);
     void solve_bcgs(const double *b, double *x, Ctx &c);
     void solve_bcgs_dev(const double *b, double *x, Ctx &c);
+    void solve_richardson(const double *b, double *x, Ctx &c);
+    void solve_chebyshev(const double *b, double *x, Ctx &c);
+    void chebyshev_estimate(Ctx &c);
+    // richardson / chebyshev: z = B r through the PC, or (returns true) left to the update kernel
+    // with PCJacobi's dinv; rn(r) of the norm type in use; out = a pm1 + b pk + c (B r)
+    const double *poly_dinv() const;
+    double poly_norm(const double *r, double *z, Ctx &c);
+    void poly_step(double a, const double *pm1, double b, const double *pk, double cz, const double *r, double *z,
+                   bool z_done, double *out, Ctx &c);
     // what the host and the device driver of a type share: the start (false: ended at iteration 0) and the end
     bool cg_begin(const double *b, double *x, Ctx &c, double &beta);
     bool bcgs_begin(const double *b, double *x, Ctx &c, double &rho0);

@@ -234,6 +234,14 @@ class Handle:
         N.check(N.lib().pls_get_gmres_orthog_stats(self.ptr, prefix.encode(), N.ptr(s)))
         return tuple(int(v) for v in s)
 
+    def chebyshev_bounds(self, prefix):
+        """(emin, emax as used, the estimate's smallest and largest real part -- NaN when the bounds
+        were given explicitly) of the chebyshev solver with this options prefix, after its first
+        solve (pls_get_chebyshev_bounds)."""
+        s = np.zeros(4, dtype=np.float64)
+        N.check(N.lib().pls_get_chebyshev_bounds(self.ptr, prefix.encode(), N.ptr(s)))
+        return tuple(float(v) for v in s)
+
     def reset_timings(self):
         N.check(N.lib().pls_reset_timings(self.ptr))
 

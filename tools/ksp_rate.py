@@ -9,6 +9,12 @@ s_ iterations they took (pls_get_ksp_stats).  The variants are run round robin
 (--rounds), so a drift of the shared machine hits all of them alike.  One JSON
 line per (variant, round).
 
+cheby_norm is Chebyshev (estimated bounds) with the preconditioned norm to the
+same rtol, one norm read back per iteration; cheby_none is Chebyshev without
+norms (no read-back, no synchronisation), its s_ksp_max_it the mean iteration
+count cheby_norm took in its warm-up solve -- so it needs cheby_norm before it
+in --variants.
+
 usage: python tools/ksp_rate.py [--N 27] [--variants bcgs_host bcgs_dev bcgs_fused gmres] [--out FILE]
        --lib PATH   load this libpls.so instead (e.g. another commit's build)
 """
@@ -30,6 +36,9 @@ VARIANTS = {
     "bcgs_dev": {"s_ksp_type": "bcgs", "pls.bcgs_device": "1", "pls.bcgs_fused_reduce": "0"},
     "bcgs_fused": {"s_ksp_type": "bcgs", "pls.bcgs_device": "1", "pls.bcgs_fused_reduce": "1"},
     "gmres": {"s_ksp_type": "gmres"},
+    "cg": {"s_ksp_type": "cg"},
+    "cheby_norm": {"s_ksp_type": "chebyshev", "s_ksp_norm_type": "preconditioned"},
+    "cheby_none": {"s_ksp_type": "chebyshev", "s_ksp_norm_type": "none"},  # + s_ksp_max_it, see above
 }
 
 
@@ -57,9 +66,15 @@ def main():
     base = {"global_ksp_type": "gmres", "global_ksp_pc_side": "right", "s_pc_type": "jacobi", "s_ksp_rtol": "1e-8",
             "fp_ksp_type": "preonly", "fp_pc_type": "ilu"}
     b = S.rhs(spec)
-    handles = {}
+    handles, max_its = {}, {}
     for v in a.variants:
         opts = dict(base, **VARIANTS[v])
+        if v == "cheby_none":
+            if "cheby_norm" not in handles:
+                raise RuntimeError("ksp_rate: cheby_none takes its max_it from cheby_norm; list that one first")
+            st = handles["cheby_norm"].ksp_stats("s_")
+            max_its[v] = max(1, round(st[1] / max(st[0], 1)))
+            opts["s_ksp_max_it"] = str(max_its[v])
         opts.update(params_to_options(params))
         h = Handle.synthetic(spec.dim, spec.N, spec.seed, spec.delta, opts)
         h.solve(b)  # warm-up: setup, code objects, work vectors
@@ -78,6 +93,8 @@ def main():
             line = {"variant": v, "round": rnd, "N": a.N, "ns": int(spec.sizes()[0]), "outer_its": its,
                     "outer_reason": reason, "s_solves": n_solves, "s_its": n_its,
                     "pc_solid_s": t["pc_solid"], "us_per_s_it": 1e6 * t["pc_solid"] / max(n_its, 1),
+                    "pc_solid_per_outer_solve_s": t["pc_solid"] / a.solves,
+                    "s_max_it": max_its.get(v, 0),
                     "solver_total_s": t["solver_total"], "lib": a.lib or "this build"}
             print(json.dumps(line), flush=True)
             if a.out:
