@@ -603,7 +603,12 @@ struct PCAMG : PC {
                 Cmat = std::move(cur);
                 const DevCSR &Cm = Cmat ? *Cmat : M;
                 if (nco <= o.integer("pls.lu_dense_max", 32768)) Clu = std::make_unique<PCDenseLU>(Cm, c);
-                else Clu = std::make_unique<PCILU>(Cm, 1, c, true, o.flag("pls.ilu_lds", true));
+                else {
+                    PCILU::Config cfg;
+                    cfg.exact_lu = true;
+                    cfg.allow_lds = o.flag("pls.ilu_lds", true);
+                    Clu = std::make_unique<PCILU>(Cm, 1, c, cfg);
+                }
             }
         }
         c.sync();

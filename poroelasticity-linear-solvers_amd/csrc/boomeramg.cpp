@@ -1502,8 +1502,10 @@ struct PCBoomer : PC {
     // extracts each chunk's block from it; a sharded one drops its ghost columns)
     void build_sets(BLevel &L, const HostCSR &Al, const std::vector<int8_t> &cf, const std::vector<int64_t> &cst,
                     bool bounds, const DevCSR &Adev, const Options &o, const std::string &prefix, Ctx &c) {
-        const bool allow_lds = o.flag("pls.ilu_lds", true);
-        const int gmem = (int)o.integer("pls.ilu_gmem", 0), ring = (int)o.integer("pls.ilu_ring", 1);
+        // the chunks' sweeps: C/F sets read the kernel options only, all-row sets the tuning ones too
+        PCILU::Config cfg = PCILU::Config::from_options(o, prefix, no_cf ? PCILU::Config::Tuning : 0);
+        cfg.sgs = true;
+        const int gmem = cfg.gmem_mode;
         // Gauss-Seidel chunks through dense inverses: -1 by the cost model below, 1 whenever
         // they fit (pls.amg_gs_dense_gb, chunks <= pls.lu_dense_max rows), 0 never
         const int gs_dense = (int)o.integer("pls.amg_gs_dense", -1);
@@ -1556,19 +1558,16 @@ struct PCBoomer : PC {
                     rs->sgs = std::make_unique<PCSGSDense>(lo, up, cp, c);
                 } else {
                     // wide levels: one grid-wide launch per level beats one workgroup
-                    const int gm = (nlev > 0 && lo.nrows / nlev > wide_rows) ? wide_mode : gmem;
+                    cfg.gmem_mode = (nlev > 0 && lo.nrows / nlev > wide_rows) ? wide_mode : gmem;
                     if (no_cf) {
                         // the chunks are PCILU's blocks (the same partition): one workgroup per chunk
-                        auto pc = std::make_unique<PCILU>(Adev, Kl, c, false, allow_lds, 0, gm, ring, true,
-                                                          bounds ? &cst : nullptr);
-                        if (o.has("pls.sweep_tpb")) pc->lds_tpb = (int)o.integer("pls.sweep_tpb", 1024);
-                        if (o.has("pls.sweep_rr")) pc->lds_rr = o.flag("pls.sweep_rr", false) && pc->use_lds && !pc->ring;
+                        cfg.bounds = bounds ? &cst : nullptr;
                         if (o.flag("pls.sweep_profile", false))
-                            pc->profile_tag = prefix + "sgs L" + std::to_string(lv.size());
-                        rs->sgs = std::move(pc);
+                            cfg.profile_tag = prefix + "sgs L" + std::to_string(lv.size());
+                        rs->sgs = std::make_unique<PCILU>(Adev, Kl, c, cfg);
                     } else {
                         upload(chunk_part(Al, g, cst, 0), rs->sub, c);
-                        rs->sgs = std::make_unique<PCILU>(rs->sub, 1, c, false, allow_lds, 0, gm, ring, true);
+                        rs->sgs = std::make_unique<PCILU>(rs->sub, 1, c, cfg);
                     }
                 }
             }

@@ -331,141 +331,6 @@ struct PCJacobi : PC {
     bool reentrant() const override { return true; }
     void apply(const double *x, double *y, Ctx &c) override;
 };
-// Level-aligned SELL-64 strict triangular factor (see kernels.hip).
-struct TriSELL {
-    int64_t nslices = 0, ngroups = 0, nblocks = 0;
-    bool blockwise = false;
-    DBuf<int64_t> sptr, gslice, goff;
-    DBuf<int32_t> slot_row, slot_len, col;
-    DBuf<double> val, sdinv;
-    std::vector<int64_t> gslice_h;
-    void apply(const double *b, double *y, Ctx &c) const;
-};
-
-// ILU(0) of the block-Jacobi truncation of M (nblocks == 1: plain ILU(0)).
-// exact_lu: the same pipeline on the profile (envelope) pattern of M -- row i
-// spans the contiguous columns [first nonzero of row i, max column of rows
-// <= i], which contains every fill entry of LU without pivoting, so the
-// "ILU" of that pattern is the exact LU factorization (PCLU).
-// Factorization: level scheduled, one wave per row.  Sweeps: level-aligned
-// SELL-64; with >= 64 blocks one workgroup per block walks its own levels,
-// otherwise one launch per global level.
-// LDS-kernel stream layout of a blockwise TriSELL (header entry per lane,
-// block-local columns; levels/groups shared with the TriSELL).
-struct LdsTri {
-    DBuf<int64_t> sptr, gslice;  // slices differ from the TriSELL's (lanes per row); groups/goff are shared
-    DBuf<int32_t> col, lpr;      // lpr: lanes per row, per block
-    DBuf<double> val;
-};
-// Ring sweep tables of one triangle (kernels.hip, k_ilu_blocks_ring)
-struct RingTri {
-    DBuf<int64_t> coff, cg, cp;  // chunks per block / first level / [start, end) positions
-    DBuf<int32_t> ord;           // position -> row (the triangle's level order)
-    DBuf<int64_t> frp;           // far dependencies per position (CSR over b0 + p)
-    DBuf<int32_t> fcol;          // ... block-local positions
-    DBuf<double> fval;           // ... factor values
-    int64_t nfar = 0;
-};
-// Chain-sweep stream of one triangle (kernels.hip, k_ilu_blocks_chain)
-struct ChainTri {
-    DBuf<int64_t> base, soff, nsl;  // per block: first entry, first slice, slice count
-    DBuf<int32_t> sz, lpr;          // per slice: size | (8 entries per lane); per block: lanes per row
-    DBuf<int32_t> col;
-    DBuf<double> val;
-};
-// Window-sweep tables of one triangle (kernels.hip, k_ilu_blocks_window)
-struct WinTri {
-    DBuf<int64_t> woff;  // per window: off-window stream offsets (nwin + 1)
-    // rec: per stream entry (value, block-local column) as 3 words -- one
-    // 12-byte load each; tinv: per window the 64 x 64 inverse of its diagonal
-    // block, column pairs [k / 2][lane][k % 2]
-    DBuf<int32_t> rec;
-    DBuf<double> tinv;
-    int64_t nwin = 0;
-};
-// Super-window sweep tables of one triangle (kernels.hip, k_ilu_blocks_swin):
-// blocks too long for LDS, in windows of 64 rows grouped into super-windows
-// whose window inverses and near streams fit LDS (see build_swin_tri)
-struct SwinTri {
-    DBuf<int64_t> bsw;         // per block: first super-window (nblocks + 1), in processing order
-    DBuf<int64_t> sw;          // per super-window: first window (global), windows, first row, end row (block-local)
-    DBuf<int64_t> wnear, wfar;  // per window: near / far SELL offsets (nwin + 1)
-    DBuf<int32_t> ncol, fcol;  // near: row - super-window's first row (LDS index); far: block-local row
-    DBuf<double> nval, fval;
-    DBuf<double> tinv;  // per window the packed triangle of the window inverse (2080 doubles)
-    int64_t lds_bytes = 0, nwin = 0, nsw = 0;
-};
-struct PCILU : PC {
-    int64_t nblocks = 1;
-    // super-window sweep (Ctx::sweep_swin): blocks too long for LDS
-    bool swin = false;
-    SwinTri Lsw, Usw;
-    // window sweep (Ctx::sweep_window): LDS-resident blocks in 64-row windows with
-    // explicit inverses of the windows' triangles (one GEMV per window)
-    bool window = false;
-    bool window_ring = false;  // (the ring variant: y-resident, an LDS ring of the recent rows)
-    int window_entries = 32;   // (the rows' most off-window entries: <= 16 loads 4 stream records per wave)
-    int window_entries_L = 32, window_entries_U = 32;  // (per triangle: 4, 6 or 8 records per wave)
-    bool window_mixed = false; // (ring variant: L by the y-resident level sweep, U by windows)
-    DBuf<int64_t> zgoff;       // (no levels: the mixed sweep's empty U for the level launch)
-    WinTri Lw, Uw;
-    DBuf<int64_t> wstart;  // per block: its first window
-    // chain sweep (Ctx::sweep_chain): LDS-resident blocks of deep, narrow level DAGs
-    bool chain = false;
-    ChainTri Lc, Uc;
-    // ring sweep (pls.ilu_ring, default on): y-resident blocks whose levels are
-    // narrow sweep in level-order position space with an LDS ring of recent values
-    bool ring = false;
-    RingTri Lr, Ur;
-    DBuf<int32_t> mapUL;  // U position -> index of the row's L-sweep value
-    std::map<hipStream_t, std::pair<DBuf<double>, DBuf<double>>> ring_scratch;  // per stream: yL, yU
-    DevCSR F;                     // truncated matrix, factored in place
-    DBuf<int64_t> diag;
-    DBuf<double> dinv;
-    TriSELL Lf, Uf;
-    LdsTri Ls, Us;            // built when the LDS kernel serves apply()
-    bool use_lds = false;  // one workgroup per block sweeps (k_ilu_blocks_lds)
-    bool lds_gmem = false;  // ... with the block solution kept in y (blocks too long for LDS)
-    int lds_tpb = 1024;     // threads per workgroup of the LDS sweep (set from the widest level; pls.sweep_tpb)
-    int lds_depth = 2;      // levels of factor data in flight in the LDS sweep (pls.sweep_depth 2 / 3 / 4)
-    bool lds_rr = false;    // round-robin level sweep (deep DAGs of ~one slice per level; pls.sweep_rr)
-    int64_t nlev_L = 0, nlev_U = 0;
-    bool allow_lds = true;  // block solution resident in LDS when it fits
-    bool exact = false;     // envelope pattern: exact LU (PCLU)
-    // gmem_mode -2: per-level launches straight from the factored CSR, 16 lanes
-    // per row (long rows, wide levels: the AMG's Gauss-Seidel triangles)
-    bool csr_levels = false;
-    DBuf<int32_t> lrowsL, lrowsU;
-    std::vector<int64_t> lptrL, lptrU;
-    std::string profile_tag;  // non-empty: dump per-block sweep timings once (option pls.sweep_profile)
-    // gmem_mode (option pls.ilu_gmem): 0 auto, 1 force the y-resident
-    // workgroup sweep (also on blocks that fit LDS), -1 never, -2 never and
-    // per-level CSR kernels instead of the SELL-64 level slices
-    // sgs: no ILU(0) -- the factors are symmetric Gauss-Seidel's (I + L D^-1, D + U;
-    // launch_sgs_factor), so apply() is one hybrid symmetric GS sweep from 0 with
-    // the blocks as hypre's thread chunks (boomeramg.cpp)
-    bool sgs = false;
-    // explicit block starts (bounds: nblocks + 1 entries from 0 to n) instead of PETSc's bjacobi sizes
-    std::vector<int64_t> bstart_h;
-    DBuf<int64_t> bstart;
-    int64_t max_len = 0;  // longest block
-    PCILU(const DevCSR &M, int64_t nblocks, Ctx &c, bool exact_lu = false, bool allow_lds = true, int force_lpr = 0,
-          int gmem_mode = 0, int ring_mode = 1, bool sgs_factors = false, const std::vector<int64_t> *bounds = nullptr);
-    bool reentrant() const override { return profile_tag.empty(); }
-    void apply(const double *x, double *y, Ctx &c) override;
-    const char *sweep_kind() const;  // which apply kernel serves this PC (pls.ilu_view)
-    // the plain LDS sweep can run a subset of its blocks (the 2-way PC's
-    // pressure-first pipeline, capi.cpp BlockPC::apply): levels (L + U) and
-    // first row of every block, host copies made at setup
-    std::vector<int64_t> block_levels_h, block_start_h, block_maxsl_h;  // maxsl: most slices of any level
-    bool can_apply_blocks() const {
-        return use_lds && !ring && !window && !chain && !swin && !lds_gmem && profile_tag.empty() && !exact && !sgs;
-    }
-    // rr_group > 0: the round-robin sweep with groups of that many waves per level (a power of two)
-    // tpb > 0: threads per workgroup for this launch; depth: levels of factor data in flight (2, or 6 with tpb <= 512)
-    void apply_blocks(const double *x, double *y, Ctx &c, int64_t b_lo, int64_t b_hi, int rr_group = 0, int tpb = 0,
-                      int depth = 2, int64_t *prof = nullptr);  // prof: nblocks x 8 wall-clock records (diagnostics)
-};
 // Exact LU of a block small enough for a dense inverse (dense.hip): K^-1 is
 // formed once (blocked Gauss-Jordan, no pivoting, like the sparse path) and
 // applied as one dense GEMV.  Chosen for -pc_type lu when n <= pls.lu_dense_max.
@@ -683,3 +548,5 @@ std::unique_ptr<KSP> make_ksp(const std::string &prefix, const Options &o, const
                               int64_t restart = 30, PC *external_pc = nullptr);
 
 }  // namespace pls
+
+#include "ilu.hpp"  // PCILU: ilu, bjacobi, the envelope lu, the AMG's Gauss-Seidel chunks
