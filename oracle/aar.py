@@ -44,7 +44,7 @@ def _householder_r(A):
 
 
 def tsqr_lstsq(F, f, rows_per_block=512):
-    """min ||f + F a|| the way libpls solves it (csrc/capi.cpp AndersonLS):
+    """min ||f + F a|| the way libpls solves it (csrc/anderson.cpp AndersonLS):
     Householder TSQR of [F | f] over 512-row chunks, then of the stacked R's
     until one is left; a = R^-1 (-z) with z the last column.  Used by the tests
     to measure how far two backward-stable solvers of the same least squares

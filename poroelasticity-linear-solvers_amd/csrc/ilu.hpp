@@ -117,7 +117,7 @@ struct PCILU : PC {
     // one workgroup per block, and not the ring sweep (what pls.sweep_rr needs)
     bool block_sweep_not_ring() const { return sweep >= Sweep::Lds && sweep != Sweep::Ring; }
     // the plain LDS sweep can run a subset of its blocks (the 2-way PC's
-    // pressure-first pipeline, capi.cpp BlockPC::apply): levels (L + U) and
+    // pressure-first pipeline, blockpc.cpp BlockPC::apply_fp_pipeline): levels (L + U) and
     // first row of every block, host copies made at setup
     std::vector<int64_t> block_levels_h, block_start_h, block_maxsl_h;  // maxsl: most slices of any level
     bool can_apply_blocks() const { return sweep == Sweep::Lds && profile_tag.empty() && !exact && !sgs; }

@@ -174,7 +174,7 @@ def test_window_ring_long_block(gpu, capfd, mixed):
     (16, 24, {"pls.fp_pipeline_rr": "4"}),
 ])
 def test_fp_pipeline_bitwise(gpu, capfd, N, blocks, variant):
-    """The 2-way PC's pressure-first pipeline (pls.fp_pipeline, capi.cpp
+    """The 2-way PC's pressure-first pipeline (pls.fp_pipeline, blockpc.cpp
     setup_fp_pipeline): the heavy pressure BJACOBI blocks of the fp block get
     their rows of t = x_fp - P_fp,s y_s first and sweep on a second stream.
     Same per-row sums and per-block sweeps as the plain path: PC applies and
