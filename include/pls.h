@@ -217,6 +217,12 @@ int pls_get_ksp_stats(pls_handle *h, const char *prefix, int64_t stats[5]);
  * 2 refine_always, 3 modified Gram-Schmidt).  An unknown prefix or a KSP of
  * another type is an error.                                                 */
 int pls_get_gmres_orthog_stats(pls_handle *h, const char *prefix, int64_t stats[3]);
+/* Coupling reuse (option pls.reuse_coupling): products with the outer operator
+ * since the last pls_reset_timings, [0] reduced ones that continued the block
+ * preconditioner's coupling product, [1] full ones; [2] 1 when the reduced
+ * path is eligible for the next solve (decided when the solver is created and
+ * again after pls_update_matrices), else 0.                                  */
+int pls_get_reuse_stats(pls_handle *h, int64_t stats[3]);
 /* The eigenvalue bounds of the chebyshev KSP with this prefix: out[0] emin and
  * [1] emax as used, [2] the smallest and [3] the largest real part of the
  * estimate's Hessenberg eigenvalues (NaN when the bounds were given with

@@ -48,6 +48,14 @@ std::vector<const KSP *> BlockPC::ksps() const {
 void BlockPC::apply(const double *x, double *y, Ctx &c) {
     Timers &T = *timers;
     T.begin(T_PC_TOTAL);
+    // coupling reuse: the product with Mfp_s also leaves its raw row sums for the outer A y
+    // that follows (the handle decided eligibility: 2-way, no mixer, plain layouts)
+    Coupling *R = coupling && coupling->eligible ? coupling : nullptr;
+    if (R) {
+        R->fresh_for = nullptr;
+        R->spans.clear();
+        R->spans_flush = T.flushes;
+    }
     if (!three_way) {
         T.begin(T_PC_SOLID);
         ksp_s->solve(x, y, c);
@@ -57,7 +65,15 @@ void BlockPC::apply(const double *x, double *y, Ctx &c) {
             apply_fp_pipeline(x, y, c);
         } else {
             // t = x_fp - P_fp,s y_s   (Preconditioner.py:232-233, fused)
-            spmv(Mfp_s, y, t_fp.p, c, -1.0, 1.0, x + ns);
+            if (R) {
+                Timers::Span sp;
+                sp.a = T.mark(c.st);
+                spmv_store_sums(Mfp_s, y, t_fp.p, c, -1.0, 1.0, x + ns, R->q.p + ns);
+                sp.b = T.mark(c.st);
+                R->spans.push_back(sp);
+            } else {
+                spmv(Mfp_s, y, t_fp.p, c, -1.0, 1.0, x + ns);
+            }
             ksp_fp->solve(t_fp.p, y + ns, c);
         }
         T.end(T_PC_FLUID);
@@ -117,6 +133,7 @@ void BlockPC::apply(const double *x, double *y, Ctx &c) {
     if (mixer.order > 0) mixer.next(y, c);                         // :248-249
     T.end(T_PC_TOTAL);
     pc_applies++;
+    if (R) R->fresh_for = y;
 }
 
 // The 2-way fp solve as a pipeline: the heavy blocks' rows of t first, their
@@ -130,14 +147,26 @@ void BlockPC::apply_fp_pipeline(const double *x, double *y, Ctx &c) {
     // pls.ilu_view 3: per-block start / end of both launches, once (diagnostics)
     DBuf<int64_t> prof;
     if (F.view >= 3 && !F.profiled) prof.alloc(F.nb * 8);
-    spmv_slices(Mfp_s, y, t_fp.p, c, -1.0, 1.0, x + ns, F.sl_hi.p, F.n_hi);
+    // (coupling reuse: both launches store their raw row sums and are timed on their streams)
+    Coupling *R = coupling && coupling->eligible ? coupling : nullptr;
+    double *q = R ? R->q.p + ns : nullptr;
+    Timers::Span sp_hi, sp_lo;
+    if (R) sp_hi.a = timers->mark(c.st);
+    spmv_slices(Mfp_s, y, t_fp.p, c, -1.0, 1.0, x + ns, F.sl_hi.p, F.n_hi, 0, q);
+    if (R) sp_hi.b = timers->mark(c.st);
     HIPCHK(hipEventRecord(F.ev_t, c.st));
     HIPCHK(hipStreamWaitEvent(c2.st, F.ev_t, 0));
     pc->apply_blocks(t_fp.p, y + ns, c2, F.b_split, F.nb, F.rr, F.tpb, F.depth, prof.p);
     HIPCHK(hipEventRecord(F.ev_p, c2.st));
     if (F.c_lo) HIPCHK(hipStreamWaitEvent(clo.st, F.ev_t, 0));
     // (pls.fp_pipeline_lds: its workgroups reserve LDS they do not use)
-    spmv_slices(Mfp_s, y, t_fp.p, clo, -1.0, 1.0, x + ns, F.sl_lo.p, F.n_lo, F.lds);
+    if (R) sp_lo.a = timers->mark(clo.st);
+    spmv_slices(Mfp_s, y, t_fp.p, clo, -1.0, 1.0, x + ns, F.sl_lo.p, F.n_lo, F.lds, q);
+    if (R) {
+        sp_lo.b = timers->mark(clo.st);
+        R->spans.push_back(sp_hi);
+        R->spans.push_back(sp_lo);
+    }
     if (F.c_lo) {
         HIPCHK(hipEventRecord(F.ev_lo, clo.st));
         HIPCHK(hipStreamWaitEvent(c.st, F.ev_lo, 0));

@@ -37,6 +37,17 @@ struct BlockPC : PC {
 
     int pc_applies = 0;
 
+    // Coupling reuse (runtime.hpp): the handle's record, set before the first apply.  Where it
+    // is eligible the product with the coupling block stores its raw row sums there.
+    Coupling *coupling = nullptr;
+    // the block an outer operator may share (2-way, no mixer, one rank; after setup), else null
+    const DevCSR *coupling_block() const {
+        return (!three_way && mixer.order == 0 && !Mfp_s.halo && Mfp_s.sell) ? &Mfp_s : nullptr;
+    }
+    Coupling *coupling_product() const override {
+        return coupling && coupling->eligible && coupling->fresh_for ? coupling : nullptr;
+    }
+
   private:
     bool three_way = false;
     int64_t ns = 0, nf = 0, np = 0;

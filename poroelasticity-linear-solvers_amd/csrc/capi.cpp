@@ -55,6 +55,8 @@ struct Handle {
     pls_result res{};
     std::vector<double> history;
     std::unique_ptr<MatOp> Aop;
+    Coupling coupling;           // the PC's coupling product reused by the outer A z (runtime.hpp)
+    bool coupling_stale = true;  // decide again before the next solve (setup, solver creation, matrix update)
 
     void parse_params() {
         pc_type = checked_pc_type(opt);
@@ -178,6 +180,9 @@ static void upload_permuted(const pls_csr *M, Handle &H, const std::vector<int64
 
 static void do_setup(Handle &H) {
     if (H.setup_done) return;
+    H.coupling.eligible = false;  // the blocks change under it: decide_coupling runs before the next solve
+    H.coupling_stale = true;
+    H.bpc.coupling = &H.coupling;
     H.bpc.setup({H.P, H.Pd, H.have_Pd, H.dist, H.distributed, H.three_way, H.ns, H.nf, H.np, H.fp_is_f, H.fp_is_p,
                  H.inner_ksp, H.inner_pc, H.opt, H.timers, H.ctx});
     H.vout.alloc(std::max<int64_t>(H.n, 1));
@@ -202,6 +207,8 @@ static void do_setup_solver(Handle &H) {
     build_sell(H.A, c);
     H.Aop = std::make_unique<MatOp>(&H.A);
     H.Aop->timers = &H.timers;
+    H.Aop->coupling = &H.coupling;
+    H.coupling_stale = true;
     if (H.solver_type == "aar") {
         H.aar.configure(o, n, atol, rtol, maxiter);
     } else {
@@ -218,9 +225,41 @@ static void do_setup_solver(Handle &H) {
     H.solver_ready = true;
 }
 
-static void solve_device(Handle &H, const double *b, double *x) {
+// Coupling reuse, decided when the preconditioner and the solver exist and again after every
+// matrix update: one rank, the 2-way PC without mixer, right-preconditioned gmres / fgmres,
+// plain D16 layouts, and the PC's coupling block bitwise A's (build_coupling).
+// pls.reuse_coupling: -1 where eligible (default), 0 never, 1 an error where not eligible.
+static void decide_coupling(Handle &H) {
+    Coupling &R = H.coupling;
+    const int64_t mode = H.opt.integer("pls.reuse_coupling", -1);
+    if (mode < -1 || mode > 1) throw Error("pls.reuse_coupling must be -1 (auto), 0 or 1");
+    R.eligible = false;
+    R.fresh_for = nullptr;
+    const KSP *k = H.outer.get();
+    std::string why;
+    if (mode == 0) why = "pls.reuse_coupling 0";
+    else if (H.distributed) why = "more than one rank";
+    else if (H.three_way) why = "3-way preconditioner";
+    else if (!k || (k->type != "gmres" && k->type != "fgmres") || !k->right)
+        why = "the outer solver is not right-preconditioned gmres or fgmres";
+    else if (!H.bpc.coupling_block()) why = "the preconditioner mixes its output (inner accel order > 0)";
+    else if (!build_coupling(H.A, H.ns, *H.bpc.coupling_block(), R, H.ctx)) why = R.why;
+    if (!R.eligible) {
+        R.reduced = DevSELL();
+        R.why = why;
+        if (mode == 1) throw Error("pls.reuse_coupling 1: the coupling product cannot be reused: " + why);
+    }
+    H.coupling_stale = false;
+}
+
+static void ensure_ready(Handle &H) {
     do_setup(H);
     do_setup_solver(H);
+    if (H.coupling_stale) decide_coupling(H);
+}
+
+static void solve_device(Handle &H, const double *b, double *x) {
+    ensure_ready(H);
     Ctx &c = H.ctx;
     H.bpc.pc_applies = 0;
     H.timers.begin(T_SOLVER);
@@ -418,9 +457,7 @@ int pls_set_option(pls_handle *hh, const char *key, const char *value) {
 }
 int pls_create_solver(pls_handle *hh) {
     PLS_TRY({
-        Handle &H = *reinterpret_cast<Handle *>(hh);
-        do_setup(H);
-        do_setup_solver(H);
+        ensure_ready(*reinterpret_cast<Handle *>(hh));
     })
 }
 
@@ -501,7 +538,10 @@ int pls_matmult_device(pls_handle *hh, const double *d_x, double *d_y) {
     PLS_TRY({
         Handle &H = *reinterpret_cast<Handle *>(hh);
         build_sell(H.A, H.ctx);
-        spmv(H.A, d_x, d_y, H.ctx);
+        // pls.reuse_coupling_probe (tests): the outer operator's product as GMRES forms it after
+        // a PC application -- reduced when d_x is what pls_pc_apply_device returned last
+        if (H.Aop && H.opt.flag("pls.reuse_coupling_probe", false)) H.Aop->apply_after(H.bpc, d_x, d_y, H.ctx);
+        else spmv(H.A, d_x, d_y, H.ctx);
         H.ctx.sync();
     })
 }
@@ -597,7 +637,22 @@ int pls_get_chebyshev_bounds(pls_handle *hh, const char *prefix, double *out) {
 int pls_hessenberg_eigenvalues(int m, const double *H, int ldh, double *re, double *im) {
     return hessenberg_eigenvalues(m, H, ldh, re, im);
 }
-int pls_reset_timings(pls_handle *hh) { PLS_TRY(reinterpret_cast<Handle *>(hh)->timers.reset()) }
+int pls_reset_timings(pls_handle *hh) {
+    PLS_TRY({
+        Handle &H = *reinterpret_cast<Handle *>(hh);
+        H.timers.reset();
+        H.coupling.n_reduced = H.coupling.n_full = 0;
+    })
+}
+int pls_get_reuse_stats(pls_handle *hh, int64_t *stats) {
+    PLS_TRY({
+        Handle &H = *reinterpret_cast<Handle *>(hh);
+        if (!stats) throw Error("pls_get_reuse_stats: null argument");
+        stats[0] = H.coupling.n_reduced;
+        stats[1] = H.coupling.n_full;
+        stats[2] = H.coupling.eligible ? 1 : 0;
+    })
+}
 
 int pls_export_matrix(pls_handle *hh, int which, int64_t *nrows, int64_t *nnz, int64_t *row_ptr, int32_t *col,
                       double *val) {
@@ -760,6 +815,8 @@ int pls_update_matrices(pls_handle *hh, const pls_csr *A, const pls_csr *P, cons
         std::vector<int64_t> inv(n);
         for (int64_t i = 0; i < n; ++i) inv[H.perm[i]] = i;
         if (A) {
+            H.coupling.eligible = false;  // (its reduced layout is of the old A)
+            H.coupling_stale = true;
             upload_permuted(A, H, inv, H.A);
             H.A.sell.reset();
             H.A.tag = 1;

@@ -2228,7 +2228,7 @@ __device__ __forceinline__ void d16_lane(int64_t sl, int lane, const int64_t *sf
 
 __global__ __launch_bounds__(TPB) void k_d16_slice_len(int64_t nslices, const int64_t *sfirst, const int32_t *slpr,
                                                        const int64_t *rp, int64_t nrows, int64_t *slen,
-                                                       const int32_t *rowmap) {
+                                                       const int32_t *rowmap, const int64_t *rstart) {
     const int64_t sl = ((int64_t)blockIdx.x * TPB + threadIdx.x) >> 6;
     const int lane = threadIdx.x & 63;
     if (sl > nslices) return;
@@ -2236,7 +2236,7 @@ __global__ __launch_bounds__(TPB) void k_d16_slice_len(int64_t nslices, const in
     int64_t row;
     int lpr, sub;
     d16_lane(sl, lane, sfirst, slpr, nrows, row, lpr, sub, rowmap);
-    const int64_t len = row >= 0 ? rp[row + 1] - rp[row] : 0;
+    const int64_t len = row >= 0 ? rp[row + 1] - (rstart ? rstart[row] : rp[row]) : 0;
     int64_t mine = len > sub ? (len - sub + lpr - 1) / lpr : 0;
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
@@ -2249,7 +2249,8 @@ __global__ __launch_bounds__(TPB) void k_d16_slice_len(int64_t nslices, const in
 // segments each lane's entry stream needs; *maxseg = max over lanes
 __global__ __launch_bounds__(TPB) void k_d16_count(int64_t nslices, const int64_t *sfirst, const int32_t *slpr,
                                                    const int64_t *rp, const int32_t *ci, int64_t nrows,
-                                                   int32_t *maxseg, const int32_t *rowmap) {
+                                                   int32_t *maxseg, const int32_t *rowmap,
+                                                   const int64_t *rstart) {
     const int64_t sl = ((int64_t)blockIdx.x * TPB + threadIdx.x) >> 6;
     const int lane = threadIdx.x & 63;
     if (sl >= nslices) return;
@@ -2257,7 +2258,7 @@ __global__ __launch_bounds__(TPB) void k_d16_count(int64_t nslices, const int64_
     int lpr, sub;
     d16_lane(sl, lane, sfirst, slpr, nrows, row, lpr, sub, rowmap);
     if (row < 0) return;
-    const int64_t s = rp[row], e = rp[row + 1];
+    const int64_t s = rstart ? rstart[row] : rp[row], e = rp[row + 1];
     int nseg = 0;
     int64_t last = -1;
     for (int64_t k = s + sub; k < e; k += lpr) {
@@ -2271,7 +2272,8 @@ __global__ __launch_bounds__(TPB) void k_d16_count(int64_t nslices, const int64_
 __global__ __launch_bounds__(TPB) void k_d16_fill(int64_t nslices, const int64_t *sfirst, const int32_t *slpr,
                                                   const int64_t *rp, const int32_t *ci, const double *val,
                                                   int64_t nrows, const int64_t *sptr, uint16_t *dl, double *dv,
-                                                  int32_t *seg, int nsegs, const int32_t *rowmap) {
+                                                  int32_t *seg, int nsegs, const int32_t *rowmap,
+                                                  const int64_t *rstart) {
     const int64_t sl = ((int64_t)blockIdx.x * TPB + threadIdx.x) >> 6;
     const int lane = threadIdx.x & 63;
     if (sl >= nslices) return;
@@ -2280,7 +2282,7 @@ __global__ __launch_bounds__(TPB) void k_d16_fill(int64_t nslices, const int64_t
     d16_lane(sl, lane, sfirst, slpr, nrows, row, lpr, sub, rowmap);
     const int64_t base = sptr[sl];
     const int64_t L = (sptr[sl + 1] - base) >> 6;
-    const int64_t s0 = row >= 0 ? rp[row] : 0;
+    const int64_t s0 = row >= 0 ? (rstart ? rstart[row] : rp[row]) : 0;
     const int64_t len = row >= 0 ? rp[row + 1] - s0 : 0;
     const int64_t slot = sl * 64 + lane;
     int nseg = 0;
@@ -2319,7 +2321,12 @@ typedef double d16_d2 __attribute__((ext_vector_type(2)));
 
 __constant__ int d16_xcd_map;  // set once by launch_d16_spmv (pls.d16_xcd)
 
-template <int G2, int TAG, bool HALO, int SEG>
+// AUX (lane-per-row slices only; a lane's row sum is one chain acc += a * x[col] in CSR
+// order, so a chain stopped after a row's first columns and continued from the stored value
+// gives the bits of the unbroken one):
+//   D16_AUX_STORE  aux[row] = acc, the raw row sum before alpha / beta
+//   D16_AUX_INIT   acc starts from aux[row] instead of 0
+template <int G2, int TAG, bool HALO, int SEG, int AUX = D16_AUX_NONE>
 __global__ __launch_bounds__(TPB) void k_d16_spmv(int64_t nrows, int64_t nslices, const int64_t *__restrict__ sptr,
                                                   const int64_t *__restrict__ sfirst,
                                                   const int32_t *__restrict__ slpr,
@@ -2328,7 +2335,7 @@ __global__ __launch_bounds__(TPB) void k_d16_spmv(int64_t nrows, int64_t nslices
                                                   double *__restrict__ y, double alpha, double beta,
                                                   const double *__restrict__ z, const double *__restrict__ ghost,
                                                   int32_t nlocal, const int32_t *__restrict__ slist,
-                                                  const int32_t *__restrict__ rowmap) {
+                                                  const int32_t *__restrict__ rowmap, double *aux) {
     static_assert(SEG == 4 || SEG == 8, "segment bases are one or two int4 per lane");
     const int lane = threadIdx.x & 63;
     // nslices: slices this launch processes -- all of them, or the subset
@@ -2357,6 +2364,7 @@ __global__ __launch_bounds__(TPB) void k_d16_spmv(int64_t nrows, int64_t nslices
     int32_t col = 0;
     int si = 0;
     double acc = 0.0;
+    if (AUX == D16_AUX_INIT && lpr == 1 && row < r1) acc = aux[row];
     const int64_t ng = L >> 3;
     for (int64_t g0 = 0; g0 < ng; g0 += G2) {
         d16_u4 d[G2];
@@ -2395,6 +2403,7 @@ __global__ __launch_bounds__(TPB) void k_d16_spmv(int64_t nrows, int64_t nslices
         if (lane % lpr) return;
     }
     if (row < r1) {
+        if (AUX == D16_AUX_STORE && lpr == 1) aux[row] = acc;
         // rowmap: slices hold rows sorted by length inside windows (SELL-C-sigma);
         // the lane's result goes to its row's place
         const int64_t yr = rowmap ? (int64_t)rowmap[row] : row;
@@ -2405,46 +2414,103 @@ __global__ __launch_bounds__(TPB) void k_d16_spmv(int64_t nrows, int64_t nslices
 }
 
 void launch_d16_slice_len(int64_t nslices, const int64_t *sfirst, const int32_t *slpr, const int64_t *rp,
-                          int64_t nrows, int64_t *slen, hipStream_t st, const int32_t *rowmap) {
-    k_d16_slice_len<<<grid_for((nslices + 1) * 64, TPB), TPB, 0, st>>>(nslices, sfirst, slpr, rp, nrows, slen, rowmap);
+                          int64_t nrows, int64_t *slen, hipStream_t st, const int32_t *rowmap, const int64_t *rstart) {
+    k_d16_slice_len<<<grid_for((nslices + 1) * 64, TPB), TPB, 0, st>>>(nslices, sfirst, slpr, rp, nrows, slen, rowmap,
+                                                                       rstart);
 }
 void launch_d16_count(int64_t nslices, const int64_t *sfirst, const int32_t *slpr, const int64_t *rp,
-                      const int32_t *ci, int64_t nrows, int32_t *maxseg, hipStream_t st, const int32_t *rowmap) {
+                      const int32_t *ci, int64_t nrows, int32_t *maxseg, hipStream_t st, const int32_t *rowmap,
+                      const int64_t *rstart) {
     if (nslices > 0)
-        k_d16_count<<<grid_for(nslices * 64, TPB), TPB, 0, st>>>(nslices, sfirst, slpr, rp, ci, nrows, maxseg, rowmap);
+        k_d16_count<<<grid_for(nslices * 64, TPB), TPB, 0, st>>>(nslices, sfirst, slpr, rp, ci, nrows, maxseg, rowmap,
+                                                                 rstart);
 }
 void launch_d16_fill(int64_t nslices, const int64_t *sfirst, const int32_t *slpr, const int64_t *rp,
                      const int32_t *ci, const double *val, int64_t nrows, const int64_t *sptr, uint16_t *dl,
-                     double *dv, int32_t *seg, int nsegs, hipStream_t st, const int32_t *rowmap) {
+                     double *dv, int32_t *seg, int nsegs, hipStream_t st, const int32_t *rowmap,
+                     const int64_t *rstart) {
     if (nslices > 0)
         k_d16_fill<<<grid_for(nslices * 64, TPB), TPB, 0, st>>>(nslices, sfirst, slpr, rp, ci, val, nrows, sptr, dl,
-                                                                dv, seg, nsegs, rowmap);
+                                                                dv, seg, nsegs, rowmap, rstart);
+}
+// see launch_coupling_rows (kernels.hpp); one thread per row
+__global__ __launch_bounds__(TPB) void k_coupling_rows(int64_t n, int64_t ns, const int64_t *rp, const int32_t *ci,
+                                                       const double *val, const int64_t *mrp, const int32_t *mci,
+                                                       const double *mval, const uint8_t *reuse, int64_t *rstart,
+                                                       int32_t *differs) {
+    const int64_t r = (int64_t)blockIdx.x * TPB + threadIdx.x;
+    if (r >= n) return;
+    const int64_t s = rp[r], e = rp[r + 1];
+    if (r < ns) {
+        rstart[r] = s;
+        return;
+    }
+    int64_t lo = s, hi = e;  // first entry with a column >= ns
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (ci[mid] < ns) lo = mid + 1;
+        else hi = mid;
+    }
+    const int64_t m0 = mrp[r - ns], cnt = lo - s;
+    bool same = mrp[r - ns + 1] - m0 == cnt;
+    for (int64_t k = 0; k < cnt && same; ++k)
+        same = ci[s + k] == mci[m0 + k] && __double_as_longlong(val[s + k]) == __double_as_longlong(mval[m0 + k]);
+    if (!same) *differs = 1;
+    rstart[r] = reuse[r] ? lo : s;
+}
+void launch_coupling_rows(int64_t n, int64_t ns, const int64_t *rp, const int32_t *ci, const double *val,
+                          const int64_t *mrp, const int32_t *mci, const double *mval, const uint8_t *reuse,
+                          int64_t *rstart, int32_t *differs, hipStream_t st) {
+    if (n > 0)
+        k_coupling_rows<<<grid_for(n, TPB), TPB, 0, st>>>(n, ns, rp, ci, val, mrp, mci, mval, reuse, rstart, differs);
 }
 void launch_first_col(int64_t nrows, const int64_t *rp, const int32_t *ci, int32_t *c0, hipStream_t st) {
     if (nrows > 0) k_first_col<<<grid_for(nrows, TPB), TPB, 0, st>>>(nrows, rp, ci, c0);
 }
-template <int G2, int SEG>
+template <int G2, int SEG, int AUX>
 static void d16_dispatch(unsigned g, hipStream_t st, int64_t nrows, int64_t ns, const int64_t *sptr,
                          const int64_t *sfirst, const int32_t *slpr, const uint16_t *dl, const double *dv,
                          const int32_t *seg, const double *x, double *y, double alpha, double beta, const double *z,
-                         int tag, const double *ghost, int32_t nl, const int32_t *slist, const int32_t *rm, size_t shm) {
+                         int tag, const double *ghost, int32_t nl, const int32_t *slist, const int32_t *rm, size_t shm,
+                         double *aux) {
     if (ghost) {
-        if (tag) k_d16_spmv<G2, 1, true, SEG><<<g, TPB, shm, st>>>(nrows, ns, sptr, sfirst, slpr, dl, dv, seg, x, y, alpha, beta, z, ghost, nl, slist, rm);
-        else k_d16_spmv<G2, 0, true, SEG><<<g, TPB, shm, st>>>(nrows, ns, sptr, sfirst, slpr, dl, dv, seg, x, y, alpha, beta, z, ghost, nl, slist, rm);
+        if (tag) k_d16_spmv<G2, 1, true, SEG, AUX><<<g, TPB, shm, st>>>(nrows, ns, sptr, sfirst, slpr, dl, dv, seg, x, y, alpha, beta, z, ghost, nl, slist, rm, aux);
+        else k_d16_spmv<G2, 0, true, SEG, AUX><<<g, TPB, shm, st>>>(nrows, ns, sptr, sfirst, slpr, dl, dv, seg, x, y, alpha, beta, z, ghost, nl, slist, rm, aux);
     } else {
-        if (tag) k_d16_spmv<G2, 1, false, SEG><<<g, TPB, shm, st>>>(nrows, ns, sptr, sfirst, slpr, dl, dv, seg, x, y, alpha, beta, z, ghost, nl, slist, rm);
-        else k_d16_spmv<G2, 0, false, SEG><<<g, TPB, shm, st>>>(nrows, ns, sptr, sfirst, slpr, dl, dv, seg, x, y, alpha, beta, z, ghost, nl, slist, rm);
+        if (tag) k_d16_spmv<G2, 1, false, SEG, AUX><<<g, TPB, shm, st>>>(nrows, ns, sptr, sfirst, slpr, dl, dv, seg, x, y, alpha, beta, z, ghost, nl, slist, rm, aux);
+        else k_d16_spmv<G2, 0, false, SEG, AUX><<<g, TPB, shm, st>>>(nrows, ns, sptr, sfirst, slpr, dl, dv, seg, x, y, alpha, beta, z, ghost, nl, slist, rm, aux);
     }
+}
+// the raw-sum store serves the block PC's coupling launches (tag 0), the initial value the
+// outer operator's reduced launch (tag 1); both on one rank only (no ghost columns)
+template <int G2, int SEG>
+static void d16_dispatch_aux(int mode, unsigned g, hipStream_t st, int64_t nrows, int64_t ns, const int64_t *sptr,
+                             const int64_t *sfirst, const int32_t *slpr, const uint16_t *dl, const double *dv,
+                             const int32_t *seg, const double *x, double *y, double alpha, double beta,
+                             const double *z, const int32_t *slist, size_t shm, double *aux) {
+    if (mode == D16_AUX_STORE)
+        k_d16_spmv<G2, 0, false, SEG, D16_AUX_STORE><<<g, TPB, shm, st>>>(nrows, ns, sptr, sfirst, slpr, dl, dv, seg, x, y, alpha, beta, z, nullptr, 0, slist, nullptr, aux);
+    else
+        k_d16_spmv<G2, 1, false, SEG, D16_AUX_INIT><<<g, TPB, shm, st>>>(nrows, ns, sptr, sfirst, slpr, dl, dv, seg, x, y, alpha, beta, z, nullptr, 0, slist, nullptr, aux);
 }
 template <int SEG>
 static void d16_unrolled(int unroll, unsigned g, hipStream_t st, int64_t nrows, int64_t nslices, const int64_t *sptr,
                          const int64_t *sfirst, const int32_t *slpr, const uint16_t *dl, const double *dv,
                          const int32_t *seg, const double *x, double *y, double alpha, double beta, const double *z,
-                         int tag, const double *ghost, int32_t nl, const int32_t *slist, const int32_t *rm, size_t shm) {
+                         int tag, const double *ghost, int32_t nl, const int32_t *slist, const int32_t *rm, size_t shm,
+                         int aux_mode, double *aux) {
+    if (aux_mode != D16_AUX_NONE) {  // (plain layouts: spmv_aux checks)
+        switch (unroll) {
+            case 1: d16_dispatch_aux<1, SEG>(aux_mode, g, st, nrows, nslices, sptr, sfirst, slpr, dl, dv, seg, x, y, alpha, beta, z, slist, shm, aux); break;
+            case 2: d16_dispatch_aux<2, SEG>(aux_mode, g, st, nrows, nslices, sptr, sfirst, slpr, dl, dv, seg, x, y, alpha, beta, z, slist, shm, aux); break;
+            default: d16_dispatch_aux<4, SEG>(aux_mode, g, st, nrows, nslices, sptr, sfirst, slpr, dl, dv, seg, x, y, alpha, beta, z, slist, shm, aux); break;
+        }
+        return;
+    }
     switch (unroll) {
-        case 1: d16_dispatch<1, SEG>(g, st, nrows, nslices, sptr, sfirst, slpr, dl, dv, seg, x, y, alpha, beta, z, tag, ghost, nl, slist, rm, shm); break;
-        case 2: d16_dispatch<2, SEG>(g, st, nrows, nslices, sptr, sfirst, slpr, dl, dv, seg, x, y, alpha, beta, z, tag, ghost, nl, slist, rm, shm); break;
-        default: d16_dispatch<4, SEG>(g, st, nrows, nslices, sptr, sfirst, slpr, dl, dv, seg, x, y, alpha, beta, z, tag, ghost, nl, slist, rm, shm); break;
+        case 1: d16_dispatch<1, SEG, D16_AUX_NONE>(g, st, nrows, nslices, sptr, sfirst, slpr, dl, dv, seg, x, y, alpha, beta, z, tag, ghost, nl, slist, rm, shm, nullptr); break;
+        case 2: d16_dispatch<2, SEG, D16_AUX_NONE>(g, st, nrows, nslices, sptr, sfirst, slpr, dl, dv, seg, x, y, alpha, beta, z, tag, ghost, nl, slist, rm, shm, nullptr); break;
+        default: d16_dispatch<4, SEG, D16_AUX_NONE>(g, st, nrows, nslices, sptr, sfirst, slpr, dl, dv, seg, x, y, alpha, beta, z, tag, ghost, nl, slist, rm, shm, nullptr); break;
     }
 }
 static int d16_xcd_host = 0;
@@ -2456,13 +2522,14 @@ void set_d16_xcd(int on) {
 void launch_d16_spmv(int64_t nrows, int64_t nslices, const int64_t *sptr, const int64_t *sfirst, const int32_t *slpr,
                      const uint16_t *dl, const double *dv, const int32_t *seg, int nsegs, const double *x, double *y,
                      double alpha, double beta, const double *z, int tag, const double *ghost, int64_t nlocal,
-                     int unroll, hipStream_t st, const int32_t *slist, const int32_t *rowmap, size_t lds_reserve) {
+                     int unroll, hipStream_t st, const int32_t *slist, const int32_t *rowmap, size_t lds_reserve,
+                     int aux_mode, double *aux) {
     if (nslices <= 0) return;
     unsigned g = grid_for(nslices, TPB / 64);
     if (d16_xcd_host) g = (g + 7) / 8 * 8;  // every XCD range the same length (surplus blocks exit)
     const int32_t nl = (int32_t)nlocal;
-    if (nsegs == 8) d16_unrolled<8>(unroll, g, st, nrows, nslices, sptr, sfirst, slpr, dl, dv, seg, x, y, alpha, beta, z, tag, ghost, nl, slist, rowmap, lds_reserve);
-    else d16_unrolled<4>(unroll, g, st, nrows, nslices, sptr, sfirst, slpr, dl, dv, seg, x, y, alpha, beta, z, tag, ghost, nl, slist, rowmap, lds_reserve);
+    if (nsegs == 8) d16_unrolled<8>(unroll, g, st, nrows, nslices, sptr, sfirst, slpr, dl, dv, seg, x, y, alpha, beta, z, tag, ghost, nl, slist, rowmap, lds_reserve, aux_mode, aux);
+    else d16_unrolled<4>(unroll, g, st, nrows, nslices, sptr, sfirst, slpr, dl, dv, seg, x, y, alpha, beta, z, tag, ghost, nl, slist, rowmap, lds_reserve, aux_mode, aux);
 }
 
 // ============================================================ SELL/B3 ======

@@ -211,16 +211,28 @@ void launch_sell_spmv(int64_t nrows, const int64_t *sptr, const int32_t *scol, c
 // SELL-64 / D16 (16-bit column deltas, D16_SEG segment bases per lane, 1 or 8 lanes per row)
 constexpr int D16_SEG = 4;      // segment bases per lane (rows of a single rank)
 constexpr int D16_SEG_MAX = 8;  // ... with halo columns (own s/f/p + a neighbour's s/f/p)
+// rstart (all three): where each row's entries begin inside [rp[row], rp[row + 1]) -- a layout
+// without the rows' first columns (the reduced outer operator); null: rp[row]
 void launch_d16_slice_len(int64_t nslices, const int64_t *sfirst, const int32_t *slpr, const int64_t *rp,
                           int64_t nrows, int64_t *slen /* nslices+1 */, hipStream_t st,
-                          const int32_t *rowmap = nullptr /* slice position -> row (SELL-C-sigma) */);
+                          const int32_t *rowmap = nullptr /* slice position -> row (SELL-C-sigma) */,
+                          const int64_t *rstart = nullptr);
 void launch_d16_count(int64_t nslices, const int64_t *sfirst, const int32_t *slpr, const int64_t *rp,
                       const int32_t *ci, int64_t nrows, int32_t *maxseg, hipStream_t st,
-                      const int32_t *rowmap = nullptr);
+                      const int32_t *rowmap = nullptr, const int64_t *rstart = nullptr);
 void launch_d16_fill(int64_t nslices, const int64_t *sfirst, const int32_t *slpr, const int64_t *rp,
                      const int32_t *ci, const double *val, int64_t nrows, const int64_t *sptr, uint16_t *dl,
                      double *dv, int32_t *seg, int nsegs /* D16_SEG or D16_SEG_MAX */, hipStream_t st,
-                     const int32_t *rowmap = nullptr);
+                     const int32_t *rowmap = nullptr, const int64_t *rstart = nullptr);
+// The coupling block of the outer operator: rows [ns, n) x columns [0, ns) of A (sorted
+// columns) against the block M the preconditioner multiplies with.  rstart[r] = the first
+// entry of row r with a column >= ns where reuse[r], else rp[r]; *differs = 1 when a row's
+// coupling entries are not M's row in count, columns and value bits.
+void launch_coupling_rows(int64_t n, int64_t ns, const int64_t *rp, const int32_t *ci, const double *val,
+                          const int64_t *mrp, const int32_t *mci, const double *mval, const uint8_t *reuse,
+                          int64_t *rstart, int32_t *differs, hipStream_t st);
+// raw row sums of lane-per-row slices (launch_d16_spmv's aux): stored, or the initial value
+constexpr int D16_AUX_NONE = 0, D16_AUX_STORE = 1, D16_AUX_INIT = 2;
 void launch_first_col(int64_t nrows, const int64_t *rp, const int32_t *ci, int32_t *c0, hipStream_t st);
 void launch_d16_spmv(int64_t nrows, int64_t nslices, const int64_t *sptr, const int64_t *sfirst, const int32_t *slpr,
                      const uint16_t *dl, const double *dv, const int32_t *seg, int nsegs, const double *x, double *y,
@@ -229,7 +241,8 @@ void launch_d16_spmv(int64_t nrows, int64_t nslices, const int64_t *sptr, const 
                      const int32_t *slist = nullptr /* nslices entries: the slices to process */,
                      const int32_t *rowmap = nullptr /* slice position -> row (SELL-C-sigma) */,
                      size_t lds_reserve = 0 /* dynamic LDS per workgroup, unused: keeps the product's
-                                               workgroups off CUs whose LDS a sweep holds */);
+                                               workgroups off CUs whose LDS a sweep holds */,
+                     int aux_mode = D16_AUX_NONE, double *aux = nullptr /* nrows: raw row sums, see D16_AUX_* */);
 // SELL/B3: row triples sharing one column list (FE vector fields), see kernels.hip
 void launch_triple_flags(int64_t n, const int64_t *rp, const int32_t *ci, uint8_t *flag, hipStream_t st);
 int b3_lanes_per_triple();

@@ -236,7 +236,7 @@ void KSP::solve_gmres(const double *b, double *x, Ctx &c) {
             if (right) {
                 double *zk = flexible ? Z.p + loc_it * ldv : t1p;
                 pc->apply(vk, zk, c);
-                A->apply(zk, vn, c);
+                A->apply_after(*pc, zk, vn, c);  // (may continue a product the PC has just formed with zk)
             } else {
                 A->apply(vk, t1p, c);
                 pc->apply(t1p, vn, c);

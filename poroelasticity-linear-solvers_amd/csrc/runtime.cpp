@@ -471,6 +471,49 @@ static bool build_sell_rcm(DevCSR &M, Ctx &c) {
     return true;
 }
 
+// The D16 arrays of M for a slice plan (sfirst, slpr, rowmap of d16_plan); rstart: see
+// launch_d16_fill.  False (S.d16 unset) when a lane needs more than D16_SEG_MAX segments.
+static bool d16_from_plan(const DevCSR &M, DevSELL &S, const std::vector<int64_t> &sf, const std::vector<int32_t> &lp,
+                          const std::vector<int32_t> &rm, const int64_t *rstart, Ctx &c) {
+    const int64_t ns = (int64_t)lp.size();
+    S.sfirst.alloc(ns + 1);
+    S.slpr.alloc(std::max<int64_t>(ns, 1));
+    HIPCHK(hipMemcpyAsync(S.sfirst.p, sf.data(), sizeof(int64_t) * (ns + 1), hipMemcpyHostToDevice, c.st));
+    HIPCHK(hipMemcpyAsync(S.slpr.p, lp.data(), sizeof(int32_t) * ns, hipMemcpyHostToDevice, c.st));
+    if (!rm.empty()) {
+        S.rowmap.alloc(rm.size());
+        S.nrows_mapped = (int64_t)rm.size();
+        HIPCHK(hipMemcpyAsync(S.rowmap.p, rm.data(), sizeof(int32_t) * rm.size(), hipMemcpyHostToDevice, c.st));
+    }
+    const int32_t *rmap = rm.empty() ? nullptr : S.rowmap.p;
+    DBuf<int32_t> mx(1);
+    HIPCHK(hipMemsetAsync(mx.p, 0, sizeof(int32_t), c.st));
+    launch_d16_count(ns, S.sfirst.p, S.slpr.p, M.rp.p, M.ci.p, M.nrows, mx.p, c.st, rmap, rstart);
+    int32_t h = 0;
+    HIPCHK(hipMemcpyAsync(&h, mx.p, sizeof(int32_t), hipMemcpyDeviceToHost, c.st));
+    c.sync();
+    S.d16 = h <= D16_SEG_MAX;
+    S.nsegs = (h <= D16_SEG && c.d16_segs <= D16_SEG) ? D16_SEG : D16_SEG_MAX;
+    if (!S.d16) return false;
+    S.nslices = ns;
+    for (int32_t l : lp) S.wide_slices += (l > 1);
+    DBuf<int64_t> slen(ns + 1);
+    launch_d16_slice_len(ns, S.sfirst.p, S.slpr.p, M.rp.p, M.nrows, slen.p, c.st, rmap, rstart);
+    S.sptr.alloc(ns + 1);
+    c.ensure_scan(ns);
+    exclusive_scan_i64(slen.p, S.sptr.p, ns, c.scan_tmp.p, c.scan_tmp_bytes, c.st);
+    HIPCHK(hipMemcpyAsync(&S.stored, S.sptr.p + ns, sizeof(int64_t), hipMemcpyDeviceToHost, c.st));
+    c.sync();
+    S.val.alloc(std::max<int64_t>(S.stored, 2));
+    S.dl.alloc(std::max<int64_t>(S.stored, 8));
+    S.seg.alloc(ns * 64 * S.nsegs);
+    launch_d16_fill(ns, S.sfirst.p, S.slpr.p, M.rp.p, M.ci.p, M.val.p, M.nrows, S.sptr.p, S.dl.p, S.val.p, S.seg.p,
+                    S.nsegs, c.st, rmap, rstart);
+    HIPCHK(hipGetLastError());
+    c.sync();
+    return true;
+}
+
 void build_sell(DevCSR &M, Ctx &c) {
     if (M.sell || M.nrows == 0) return;
     if (c.spmv_rcm != 0 && c.sell_d16 && !c.spmv_b3 && !M.halo && M.nrows == M.ncols && M.nrows >= 16384) {
@@ -495,41 +538,7 @@ void build_sell(DevCSR &M, Ctx &c) {
             M.sell = std::move(S);
             return;
         }
-        S->sfirst.alloc(ns + 1);
-        S->slpr.alloc(std::max<int64_t>(ns, 1));
-        HIPCHK(hipMemcpyAsync(S->sfirst.p, sf.data(), sizeof(int64_t) * (ns + 1), hipMemcpyHostToDevice, c.st));
-        HIPCHK(hipMemcpyAsync(S->slpr.p, lp.data(), sizeof(int32_t) * ns, hipMemcpyHostToDevice, c.st));
-        if (!rm.empty()) {
-            S->rowmap.alloc(rm.size());
-            S->nrows_mapped = (int64_t)rm.size();
-            HIPCHK(hipMemcpyAsync(S->rowmap.p, rm.data(), sizeof(int32_t) * rm.size(), hipMemcpyHostToDevice, c.st));
-        }
-        const int32_t *rmap = rm.empty() ? nullptr : S->rowmap.p;
-        DBuf<int32_t> mx(1);
-        HIPCHK(hipMemsetAsync(mx.p, 0, sizeof(int32_t), c.st));
-        launch_d16_count(ns, S->sfirst.p, S->slpr.p, M.rp.p, M.ci.p, M.nrows, mx.p, c.st, rmap);
-        int32_t h = 0;
-        HIPCHK(hipMemcpyAsync(&h, mx.p, sizeof(int32_t), hipMemcpyDeviceToHost, c.st));
-        c.sync();
-        S->d16 = h <= D16_SEG_MAX;
-        S->nsegs = (h <= D16_SEG && c.d16_segs <= D16_SEG) ? D16_SEG : D16_SEG_MAX;
-        if (S->d16) {
-            S->nslices = ns;
-            for (int32_t l : lp) S->wide_slices += (l > 1);
-            DBuf<int64_t> slen(ns + 1);
-            launch_d16_slice_len(ns, S->sfirst.p, S->slpr.p, M.rp.p, M.nrows, slen.p, c.st, rmap);
-            S->sptr.alloc(ns + 1);
-            c.ensure_scan(ns);
-            exclusive_scan_i64(slen.p, S->sptr.p, ns, c.scan_tmp.p, c.scan_tmp_bytes, c.st);
-            HIPCHK(hipMemcpyAsync(&S->stored, S->sptr.p + ns, sizeof(int64_t), hipMemcpyDeviceToHost, c.st));
-            c.sync();
-            S->val.alloc(std::max<int64_t>(S->stored, 2));
-            S->dl.alloc(std::max<int64_t>(S->stored, 8));
-            S->seg.alloc(ns * 64 * S->nsegs);
-            launch_d16_fill(ns, S->sfirst.p, S->slpr.p, M.rp.p, M.ci.p, M.val.p, M.nrows, S->sptr.p, S->dl.p,
-                            S->val.p, S->seg.p, S->nsegs, c.st, rmap);
-            HIPCHK(hipGetLastError());
-            c.sync();
+        if (d16_from_plan(M, *S, sf, lp, rm, nullptr, c)) {
             M.sell = std::move(S);
             if (M.halo) classify_halo_slices(M, c);
             return;
@@ -653,13 +662,91 @@ void spmv(const DevCSR &M, const double *x, double *y, Ctx &c, double alpha, dou
 
 // the slices slist[0 .. count) of a D16 layout (rows of those slices only; the
 // per-row sums are spmv()'s): the 2-way PC's pressure-first pipeline
+bool plain_d16(const DevCSR &M) {
+    return M.sell && M.sell->d16 && !M.halo && !M.sell->nperm && !M.sell->b3_nslices && !M.sell->nrows_mapped;
+}
+
 void spmv_slices(const DevCSR &M, const double *x, double *y, Ctx &c, double alpha, double beta, const double *z,
-                 const int32_t *slist, int64_t count, size_t lds_reserve) {
-    if (!M.sell || !M.sell->d16 || M.halo || M.sell->nperm || M.sell->b3_nslices || M.sell->nrows_mapped)
-        throw Error("spmv_slices: plain D16 layouts only");
+                 const int32_t *slist, int64_t count, size_t lds_reserve, double *qout) {
+    if (!plain_d16(M)) throw Error("spmv_slices: plain D16 layouts only");
+    if (qout && M.tag) throw Error("spmv_slices: raw row sums are stored for inner matrices only");
     const DevSELL &S = *M.sell;
     launch_d16_spmv(M.nrows, count, S.sptr.p, S.sfirst.p, S.slpr.p, S.dl.p, S.val.p, S.seg.p, S.nsegs, x, y, alpha, beta,
-                    z, M.tag, nullptr, M.ncols, c.d16_unroll, c.st, slist, nullptr, lds_reserve);
+                    z, M.tag, nullptr, M.ncols, c.d16_unroll, c.st, slist, nullptr, lds_reserve,
+                    qout ? D16_AUX_STORE : D16_AUX_NONE, qout);
+}
+
+void spmv_store_sums(const DevCSR &M, const double *x, double *y, Ctx &c, double alpha, double beta, const double *z,
+                     double *qout) {
+    if (!plain_d16(M) || M.tag) throw Error("spmv_store_sums: plain D16 layouts of inner matrices only");
+    const DevSELL &S = *M.sell;
+    launch_d16_spmv(M.nrows, S.nslices, S.sptr.p, S.sfirst.p, S.slpr.p, S.dl.p, S.val.p, S.seg.p, S.nsegs, x, y, alpha,
+                    beta, z, 0, nullptr, M.ncols, c.d16_unroll, c.st, nullptr, nullptr, 0, D16_AUX_STORE, qout);
+}
+
+// ======================================================= coupling reuse ===
+bool build_coupling(const DevCSR &A, int64_t ns, const DevCSR &M, Coupling &R, Ctx &c) {
+    R.eligible = false;
+    R.fresh_for = nullptr;
+    R.reduced = DevSELL();
+    R.reuse_rows = 0;
+    const int64_t n = A.nrows;
+    if (!plain_d16(A) || !plain_d16(M)) {
+        R.why = "the outer operator's or the coupling block's layout is not plain D16";
+        return false;
+    }
+    if (M.nrows != n - ns || M.ncols != ns || A.ncols != n) {
+        R.why = "the coupling block is not rows [ns, n) x columns [0, ns) of the outer operator";
+        return false;
+    }
+    // reuse rows: lane-per-row in A's plan and in M's
+    const DevSELL &SA = *A.sell, &SM = *M.sell;
+    std::vector<int64_t> sfa(SA.nslices + 1), sfm(SM.nslices + 1);
+    std::vector<int32_t> lpa(SA.nslices), lpm(SM.nslices);
+    HIPCHK(hipMemcpyAsync(sfa.data(), SA.sfirst.p, sizeof(int64_t) * sfa.size(), hipMemcpyDeviceToHost, c.st));
+    HIPCHK(hipMemcpyAsync(lpa.data(), SA.slpr.p, sizeof(int32_t) * lpa.size(), hipMemcpyDeviceToHost, c.st));
+    HIPCHK(hipMemcpyAsync(sfm.data(), SM.sfirst.p, sizeof(int64_t) * sfm.size(), hipMemcpyDeviceToHost, c.st));
+    HIPCHK(hipMemcpyAsync(lpm.data(), SM.slpr.p, sizeof(int32_t) * lpm.size(), hipMemcpyDeviceToHost, c.st));
+    c.sync();
+    std::vector<uint8_t> reuse(n, 0);
+    for (int64_t s = 0; s < SM.nslices; ++s)
+        if (lpm[s] == 1)
+            for (int64_t r = sfm[s]; r < std::min(sfm[s + 1], M.nrows); ++r) reuse[ns + r] = 1;
+    for (int64_t s = 0; s < SA.nslices; ++s)
+        for (int64_t r = sfa[s]; r < std::min(sfa[s + 1], n); ++r) {
+            if (lpa[s] != 1) reuse[r] = 0;
+            R.reuse_rows += reuse[r];
+        }
+    DBuf<uint8_t> dreuse(n);
+    DBuf<int64_t> rstart(n);
+    DBuf<int32_t> differs(1);
+    HIPCHK(hipMemcpyAsync(dreuse.p, reuse.data(), n, hipMemcpyHostToDevice, c.st));
+    HIPCHK(hipMemsetAsync(differs.p, 0, sizeof(int32_t), c.st));
+    launch_coupling_rows(n, ns, A.rp.p, A.ci.p, A.val.p, M.rp.p, M.ci.p, M.val.p, dreuse.p, rstart.p, differs.p, c.st);
+    HIPCHK(hipGetLastError());
+    int32_t diff = 0;
+    HIPCHK(hipMemcpyAsync(&diff, differs.p, sizeof(int32_t), hipMemcpyDeviceToHost, c.st));
+    c.sync();
+    if (diff) {
+        R.why = "the preconditioner's coupling block differs from the outer operator's";
+        return false;
+    }
+    if (R.reuse_rows == 0) {
+        R.why = "no row is lane-per-row in both layouts";
+        return false;
+    }
+    // A' on A's own slice plan: a reuse row stays lane-per-row whatever is left of it
+    if (!d16_from_plan(A, R.reduced, sfa, lpa, {}, rstart.p, c)) {
+        R.why = "the reduced layout does not fit D16";
+        R.reduced = DevSELL();
+        return false;
+    }
+    if (R.q.n != (size_t)n) R.q.alloc(n);
+    HIPCHK(hipMemsetAsync(R.q.p, 0, sizeof(double) * n, c.st));
+    c.sync();
+    R.why.clear();
+    R.eligible = true;
+    return true;
 }
 
 // ============================================================== options ===
@@ -742,6 +829,13 @@ void Timers::flush() {
     }
     pending.clear();
     if (open_stack.empty()) next = 0;
+    ++flushes;
+}
+hipEvent_t Timers::mark(hipStream_t s) {
+    if (!enabled) return nullptr;
+    hipEvent_t e = ev();
+    HIPCHK(hipEventRecord(e, s));
+    return e;
 }
 
 void MatOp::apply(const double *x, double *y, Ctx &c) {
@@ -749,6 +843,28 @@ void MatOp::apply(const double *x, double *y, Ctx &c) {
     if (timers) timers->begin(T_SPMV);
     spmv(*M, x, y, c);
     if (timers) { timers->end(T_SPMV); timers->spmv_calls++; }
+    if (coupling) coupling->n_full++;
+}
+
+// The reduced product where the PC's coupling sums belong to x, else the full one.  T_SPMV
+// gets the reduced launch and the coupling launches that produced q (together they stream
+// the whole of A once), as one call.
+void MatOp::apply_after(const PC &pc, const double *x, double *y, Ctx &c) {
+    Coupling *R = coupling;
+    if (!R || !R->eligible || pc.coupling_product() != R || R->fresh_for != x) return apply(x, y, c);
+    R->fresh_for = nullptr;
+    const DevSELL &S = R->reduced;
+    if (timers) timers->begin(T_SPMV);
+    launch_d16_spmv(M->nrows, S.nslices, S.sptr.p, S.sfirst.p, S.slpr.p, S.dl.p, S.val.p, S.seg.p, S.nsegs, x, y, 1.0,
+                    0.0, nullptr, 1, nullptr, M->ncols, c.d16_unroll, c.st, nullptr, nullptr, 0, D16_AUX_INIT, R->q.p);
+    if (timers) {
+        timers->end(T_SPMV);
+        timers->spmv_calls++;
+        if (R->spans_flush == timers->flushes)
+            for (const Timers::Span &sp : R->spans) timers->add(T_SPMV, sp);
+    }
+    R->spans.clear();
+    R->n_reduced++;
 }
 
 void Op::residual(const double *x, const double *b, double *r, Ctx &c) {
@@ -760,6 +876,7 @@ void MatOp::residual(const double *x, const double *b, double *r, Ctx &c) {
     if (timers) timers->begin(T_SPMV);
     spmv(*M, x, r, c, -1.0, 1.0, b);
     if (timers) { timers->end(T_SPMV); timers->spmv_calls++; }
+    if (coupling) coupling->n_full++;
 }
 
 // ====================================================== preconditioners ===

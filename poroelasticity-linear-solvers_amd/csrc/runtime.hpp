@@ -206,8 +206,14 @@ void extract_csr(const DevCSR &src, int64_t r0, int64_t r1, WindowSpec w, int64_
 void classify_halo_slices(DevCSR &M, Ctx &c);
 void spmv(const DevCSR &M, const double *x, double *y, Ctx &c, double alpha = 1.0, double beta = 0.0,
           const double *z = nullptr);
+// qout (plain D16 layouts): also qout[row] = the raw row sum, before alpha and beta, for the
+// rows of lane-per-row slices (launch_d16_spmv's D16_AUX_STORE)
 void spmv_slices(const DevCSR &M, const double *x, double *y, Ctx &c, double alpha, double beta, const double *z,
-                 const int32_t *slist, int64_t count, size_t lds_reserve = 0);
+                 const int32_t *slist, int64_t count, size_t lds_reserve = 0, double *qout = nullptr);
+void spmv_store_sums(const DevCSR &M, const double *x, double *y, Ctx &c, double alpha, double beta, const double *z,
+                     double *qout);
+// true when M's layout is the plain D16 one (no halo, RCM relabelling, row triples or row map)
+bool plain_d16(const DevCSR &M);
 
 // Host copy of a CSR matrix (setup-time algebra: fieldsplit blocks, AMG hierarchy).
 // std::allocator whose value-initialisation is default-initialisation: a
@@ -273,6 +279,8 @@ struct Options {
 // -------------------------------------------------------------- timer pool --
 enum TimerCat { T_PC_TOTAL = 0, T_PC_SOLID, T_PC_FLUID, T_PC_PRESS, T_PC_ALLOC, T_SOLVER, T_SPMV, T_NCAT };
 struct Timers {
+    // an interval on any stream, outside the begin / end nesting (see add)
+    struct Span { hipEvent_t a = nullptr, b = nullptr; };
     double acc[T_NCAT] = {0};
     int64_t spmv_calls = 0;
     bool enabled = true;
@@ -289,13 +297,46 @@ struct Timers {
     void end(int cat);
     void flush();  // call after a stream sync
     void reset() { for (double &a : acc) a = 0; spmv_calls = 0; }
+    // Non-nesting intervals: mark(s) records an event of the pool on stream s; add(cat, span)
+    // counts the time between two marks into cat at the next flush.  A span is valid until
+    // that flush (`flushes` tells: the pool's events are handed out again after it).
+    hipEvent_t mark(hipStream_t s);
+    void add(int cat, Span sp) { if (enabled && sp.a && sp.b) pending.push_back({cat, sp.a, sp.b}); }
+    int64_t flushes = 0;
 };
 
+// ------------------------------------------- coupling reuse (outer product) --
+// Right-preconditioned GMRES forms w = A z directly after z = M^-1 v.  The 2-way block PC has
+// then just multiplied its coupling block P_fp,s with z_s; where that block is A's own
+// (rows [ns, n) x columns [0, ns), bitwise), the PC's launches also store their raw row sums
+// q, and the outer product runs over `reduced` -- A without those entries on the reuse rows
+// -- starting each such row's sum from q.  Same chain of operations per row as the full
+// product, so the same bits ("Coupling reuse").  Owned by the handle; the block PC
+// writes q and the spans, MatOp consumes them.
+struct Coupling {
+    bool eligible = false;     // decided at setup and after every matrix update
+    std::string why;           // ... and why not
+    DevSELL reduced;           // second D16 layout of the outer operator (A's slice plan)
+    int64_t reuse_rows = 0;
+    DBuf<double> q;            // n: raw sums on the reuse rows; zero wherever the reduced launch reads it else
+    const double *fresh_for = nullptr;  // the z the PC returned last, while q belongs to it
+    std::vector<Timers::Span> spans;    // the PC's coupling launches of that application
+    int64_t spans_flush = -1;
+    int64_t n_reduced = 0, n_full = 0;  // outer products since the last reset
+};
+// Decide the layout-level conditions and build `reduced` and q: both layouts plain D16, A's
+// coupling entries bitwise those of M (device comparison).  Returns false with R.why set.
+bool build_coupling(const DevCSR &A, int64_t ns, const DevCSR &M, Coupling &R, Ctx &c);
+
 // --------------------------------------------------------------- operators --
+struct PC;
 struct Op {
     int64_t n = 0;
     virtual ~Op() = default;
     virtual void apply(const double *x, double *y, Ctx &c) = 0;
+    // y = A x for the x that pc.apply() has just returned: an operator that shares work with
+    // that application (MatOp with a Coupling) may continue it
+    virtual void apply_after(const PC &pc, const double *x, double *y, Ctx &c) { apply(x, y, c); }
     // r = b - A x (r is neither x nor b); a matrix does it in the product's launch
     virtual void residual(const double *x, const double *b, double *r, Ctx &c);
 };
@@ -304,7 +345,9 @@ struct MatOp : Op {
     Timers *timers = nullptr;
     explicit MatOp(const DevCSR *m) : M(m) { n = m->nrows; }
     Ctx *ctx_for_build = nullptr;
+    Coupling *coupling = nullptr;  // the outer operator's (counts its products; reduced ones where eligible)
     void apply(const double *x, double *y, Ctx &c) override;
+    void apply_after(const PC &pc, const double *x, double *y, Ctx &c) override;
     void residual(const double *x, const double *b, double *r, Ctx &c) override;
 };
 
@@ -319,6 +362,8 @@ struct PC {
     // apply() runs a KSP of its own (fieldsplit, the block PC): iterations a
     // device-resident outer loop enqueues past its end would count as inner solves
     virtual bool holds_ksp() const { return false; }
+    // the coupling product that belongs to the y apply() returned last (null: none)
+    virtual Coupling *coupling_product() const { return nullptr; }
 };
 struct PCNone : PC {
     explicit PCNone(int64_t n_) { type = "none"; n = n_; }

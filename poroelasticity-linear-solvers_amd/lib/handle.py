@@ -242,6 +242,13 @@ class Handle:
         N.check(N.lib().pls_get_chebyshev_bounds(self.ptr, prefix.encode(), N.ptr(s)))
         return tuple(float(v) for v in s)
 
+    def reuse_stats(self):
+        """(reduced outer products, full outer products since the last reset_timings, eligible 0/1)
+        of the coupling reuse (pls_get_reuse_stats)."""
+        s = np.zeros(3, dtype=np.int64)
+        N.check(N.lib().pls_get_reuse_stats(self.ptr, N.ptr(s)))
+        return tuple(int(v) for v in s)
+
     def reset_timings(self):
         N.check(N.lib().pls_reset_timings(self.ptr))
 
