@@ -112,7 +112,14 @@ int pls_set_device(int device);
  * Gram-Schmidt ("<prefix>ksp_gmres_modifiedgramschmidt", which wins over the
  * classical flag, as in PETSc, and ignores the refinement type).  Other KSP
  * types ignore the three.  "pls.gmres_mgs_fused 1" finishes each modified
- * Gram-Schmidt sum in the step's own launch (one rank; bitwise the default). */
+ * Gram-Schmidt sum in the step's own launch (one rank; bitwise the default).
+ * Levels of fill: "<prefix>pc_factor_levels k" for pc_type ilu and
+ * "<prefix>sub_pc_factor_levels k" for bjacobi's ilu blocks (each block's own
+ * truncated matrix) factor on PETSc's ILU(k) pattern (natural ordering, sum
+ * rule; built on the device); k = 0, the default, is ILU(0).  A negative or
+ * non-integer k is an error that names the key; so are a filled row longer
+ * than the factorization stages and a filled pattern beyond the free device
+ * memory.  pls_get_ilu_fill reports the fill.                                */
 
 /* Build a solver from host CSR matrices in the caller's (e.g. dolfin
  * interleaved) ordering plus the field index sets (sorted global indices of
@@ -229,6 +236,12 @@ int pls_get_reuse_stats(pls_handle *h, int64_t stats[3]);
  * <prefix>ksp_chebyshev_eigenvalues).  An unknown prefix, a KSP of another type
  * or one that has not run a solve since it was set up is an error.           */
 int pls_get_chebyshev_bounds(pls_handle *h, const char *prefix, double out[4]);
+/* Levels of fill of the ilu / bjacobi(ilu) PC of the KSP with this prefix:
+ * stats[0] the levels k (<prefix>pc_factor_levels, <prefix>sub_pc_factor_levels),
+ * [1] stored entries of the (block-truncated) matrix before the fill, [2] after
+ * it (the factors' entries), [3] the longest filled row.  With k = 0, [2] = [1].
+ * An unknown prefix, or a PC that is not ILU / BJACOBI(ILU), is an error.     */
+int pls_get_ilu_fill(pls_handle *h, const char *prefix, int64_t stats[4]);
 /* Eigenvalues of the leading m x m part (1 <= m <= 64) of an upper Hessenberg
  * matrix stored by columns, H[i + j * ldh]; entries below the subdiagonal are
  * not read.  Host code (shifted QR, no LAPACK, no device): re[k] + i im[k], in

@@ -634,7 +634,20 @@ int pls_get_chebyshev_bounds(pls_handle *hh, const char *prefix, double *out) {
         out[3] = found->cheb_raw[1];
     })
 }
-int pls_hessenberg_eigenvalues(int m, const double *H, int ldh, double *re, double *im) {
+int pls_get_ilu_fill(pls_handle *hh, const char *prefix, int64_t *stats) {
+    PLS_TRY({
+        const KSP *found = find_ksp(*reinterpret_cast<Handle *>(hh), prefix, stats, "pls_get_ilu_fill");
+        const PCILU *ilu = found->pc ? dynamic_cast<const PCILU *>(found->pc->unwrapped()) : nullptr;
+        if (!ilu || ilu->exact || ilu->sgs)
+            throw Error("pls_get_ilu_fill: the PC with prefix '" + found->prefix + "' is of type " +
+                        (found->pc ? found->pc->type : std::string("none")) + ", not ilu or bjacobi with ilu blocks");
+        stats[0] = ilu->levels;
+        stats[1] = ilu->nnz_block;
+        stats[2] = ilu->F.nnz;
+        stats[3] = ilu->F.max_row;
+    })
+}
+int pls_hessenberg_eigenvalues(int m,const double *H, int ldh, double *re, double *im) {
     return hessenberg_eigenvalues(m, H, ldh, re, im);
 }
 int pls_reset_timings(pls_handle *hh) {

@@ -1,4 +1,5 @@
-// ilu.cpp -- PCILU: ILU(0) of a matrix's block-Jacobi truncation (ilu, bjacobi), the exact LU on its
+// ilu.cpp -- PCILU: ILU(0) of a matrix's block-Jacobi truncation (ilu, bjacobi; ILU(k) where levels of
+// fill are asked for: fill_levels swaps the pattern before the factorization), the exact LU on its
 // envelope pattern (lu) and the classical AMG's hybrid Gauss-Seidel chunks (sgs).  The constructor
 // factors (factor), picks one of ten sweep kernels (choose_sweep) and builds that kernel's device
 // tables from the factors (build_tables); apply() launches it.
@@ -837,7 +838,142 @@ PCILU::Config PCILU::Config::from_options(const Options &o, const std::string &p
         if (cfg.lds_depth < 2 || cfg.lds_depth > 4) throw Error(k + " must be 2, 3 or 4");
     }
     if (reads & Tuning) cfg.rr = o.flag("pls.sweep_rr", false);
+    if (reads & (Levels | SubLevels)) {
+        const std::string k = prefix + ((reads & SubLevels) ? "sub_pc_factor_levels" : "pc_factor_levels");
+        const std::string v = o.str(k, "");
+        if (!v.empty()) {
+            size_t used = 0;
+            long long lv = -1;
+            try { lv = std::stoll(v, &used); } catch (...) { used = 0; }
+            if (used != v.size() || lv < 0 || lv > INT_MAX)
+                throw Error("option " + k + ": levels of fill must be a non-negative integer, got '" + v + "'");
+            cfg.levels = (int)lv;
+            cfg.levels_key = k;
+        }
+        cfg.iluk_lds_slots = (int)o.integer("pls.iluk_lds_slots", 0);
+        const int sl = cfg.iluk_lds_slots;
+        if (sl != 0 && (sl < 256 || sl > 8192 || (sl & (sl - 1))))
+            throw Error("pls.iluk_lds_slots " + std::to_string(sl) + ": a power of two from 256 to 8192 (0: automatic)");
+    }
     return cfg;
+}
+
+// F <- the ILU(k) pattern of F (iluk.hip: two searches per row, count / scan / fill / sort), F's
+// values in their places and zeros in the new ones.  F is the truncated block, so bjacobi's
+// blocks fill separately.
+void PCILU::fill_levels(Ctx &c, const Config &cfg) {
+    const int64_t n = F.nrows;
+    const std::string who = "ILU(" + std::to_string(cfg.levels) + ") symbolic (" + cfg.levels_key + ")";
+    if (n == 0) return;
+    DBuf<int32_t> fail(1);
+    HIPCHK(hipMemsetAsync(fail.p, 0, sizeof(int32_t), c.st));
+    auto failed = [&] {
+        int32_t h = 0;
+        HIPCHK(hipMemcpyAsync(&h, fail.p, sizeof(int32_t), hipMemcpyDeviceToHost, c.st));
+        c.sync();
+        return h;
+    };
+    {  // every row needs its diagonal entry: the filled pattern would otherwise invent it
+        DBuf<int64_t> dpos(n);
+        launch_find_diag(n, F.rp.p, F.ci.p, dpos.p, fail.p, c.st);
+        if (failed()) throw Error("ILU(0): missing diagonal entry (PETSc: MAT_FACTOR_STRUCT_ZEROPIVOT)");
+    }
+    // G(A^T): the block's transposed pattern (unsorted adjacency lists)
+    DBuf<int64_t> tcnt(n + 1), trp(n + 1);
+    DBuf<int32_t> tci(std::max<int64_t>(F.nnz, 1)), cursor(n);
+    HIPCHK(hipMemsetAsync(tcnt.p, 0, sizeof(int64_t) * (n + 1), c.st));
+    HIPCHK(hipMemsetAsync(cursor.p, 0, sizeof(int32_t) * n, c.st));
+    launch_iluk_transpose_count(n, F.rp.p, F.ci.p, tcnt.p, c.st);
+    c.ensure_scan(n);
+    exclusive_scan_i64(tcnt.p, trp.p, n, c.scan_tmp.p, c.scan_tmp_bytes, c.st);
+    launch_iluk_transpose_fill(n, F.rp.p, F.ci.p, trp.p, cursor.p, tci.p, c.st);
+    HIPCHK(hipGetLastError());
+    // LDS table of a search: 16 k r slots for rows of at most r entries (half of them usable), 1.8
+    // to 48 KB per wave.  Measured on the 2-D N = 6 blocks (r = 23 / 42): 8 r slots held every
+    // level-1 search but sent 522 of 676 and 64 of 774 level-2 searches to the global-memory
+    // launch, which clears a 131,072-slot table per search; the visited set (vertices < i
+    // included) grows faster with the level than the filled row does
+    int slot_bits = 8;
+    if (cfg.iluk_lds_slots) {
+        while ((1 << slot_bits) < cfg.iluk_lds_slots) ++slot_bits;
+    } else {
+        while (slot_bits < 13 && (1 << slot_bits) < 16 * (int64_t)cfg.levels * F.max_row) ++slot_bits;
+    }
+    const int gbits = 17;  // global-memory tables: 65,536 visited vertices per search
+    DBuf<int32_t> lcnt(n), ucnt(n), ovfA(n), ovfT(n), ovfn(2);
+    HIPCHK(hipMemsetAsync(lcnt.p, 0, sizeof(int32_t) * n, c.st));
+    HIPCHK(hipMemsetAsync(ovfn.p, 0, sizeof(int32_t) * 2, c.st));
+    IlukSearch sa{};
+    sa.n = n, sa.rp = F.rp.p, sa.ci = F.ci.p, sa.levels = cfg.levels, sa.slot_bits = slot_bits, sa.transposed = 0;
+    sa.lcnt = lcnt.p, sa.ucnt = ucnt.p, sa.ovf_rows = ovfA.p, sa.ovf_n = ovfn.p, sa.fail = fail.p;
+    IlukSearch st = sa;
+    st.rp = trp.p, st.ci = tci.p, st.transposed = 1, st.ovf_rows = ovfT.p, st.ovf_n = ovfn.p + 1;
+    int32_t nov[2] = {0, 0};
+    DBuf<int> gtab;
+    int ggrid = 0;
+    auto pass = [&](bool fill) {
+        launch_iluk_search(sa, fill, c.st);
+        launch_iluk_search(st, fill, c.st);
+        HIPCHK(hipGetLastError());
+        if (!fill) {
+            HIPCHK(hipMemcpyAsync(nov, ovfn.p, sizeof(nov), hipMemcpyDeviceToHost, c.st));
+            c.sync();
+            if (nov[0] + nov[1] > 0) {
+                ggrid = (int)std::min<int64_t>(std::max(nov[0], nov[1]), 256);
+                gtab.alloc((size_t)ggrid * iluk_search_table_ints(1 << gbits));
+            }
+        }
+        IlukSearch ga = sa, gt = st;
+        ga.slot_bits = gt.slot_bits = gbits;
+        launch_iluk_search_gmem(ga, fill, nov[0], std::min<int>(ggrid, std::max(nov[0], 1)), gtab.p, c.st);
+        launch_iluk_search_gmem(gt, fill, nov[1], std::min<int>(ggrid, std::max(nov[1], 1)), gtab.p, c.st);
+        HIPCHK(hipGetLastError());
+        if (failed())
+            throw Error(who + ": a row's search visits more than " + std::to_string(1 << (gbits - 1)) +
+                        " vertices; lower the levels of fill");
+    };
+    pass(false);
+    iluk_gmem_rows = (int64_t)nov[0] + nov[1];
+    // row lengths -> row pointers; the refusals
+    DevCSR G;
+    DBuf<int64_t> len(n + 1);
+    G.rp.alloc(n + 1);
+    launch_iluk_row_len(n, lcnt.p, ucnt.p, len.p, c.st);
+    exclusive_scan_i64(len.p, G.rp.p, n, c.scan_tmp.p, c.scan_tmp_bytes, c.st);
+    std::vector<int64_t> hrp(n + 1);
+    HIPCHK(hipMemcpyAsync(hrp.data(), G.rp.p, sizeof(int64_t) * (n + 1), hipMemcpyDeviceToHost, c.st));
+    c.sync();
+    int64_t mr = 0;
+    for (int64_t i = 0; i < n; ++i) mr = std::max(mr, hrp[i + 1] - hrp[i]);
+    if (mr > ilu0_max_row())
+        throw Error(who + ": a filled row has " + std::to_string(mr) + " entries, the factorization stages at most " +
+                    std::to_string(ilu0_max_row()) + " per row; lower " + cfg.levels_key);
+    const int64_t fnnz = hrp[n];
+    size_t free_b = 0, total_b = 0;
+    HIPCHK(hipMemGetInfo(&free_b, &total_b));
+    // (columns and values now, the sweep tables -- about as much again -- later)
+    if (fnnz < 0 || fnnz > INT64_MAX / 64 || (double)fnnz * 12.0 > 0.9 * (double)free_b)
+        throw Error(who + ": the filled pattern has " + std::to_string(fnnz) + " entries (" +
+                    std::to_string(fnnz * 12 >> 20) + " MiB), " + std::to_string(free_b >> 20) +
+                    " MiB of device memory are free; lower " + cfg.levels_key);
+    G.ci.alloc(std::max<int64_t>(fnnz, 1));
+    G.val.alloc(std::max<int64_t>(fnnz, 1));
+    HIPCHK(hipMemsetAsync(G.val.p, 0, sizeof(double) * std::max<int64_t>(fnnz, 1), c.st));
+    HIPCHK(hipMemsetAsync(cursor.p, 0, sizeof(int32_t) * n, c.st));
+    sa.orp = st.orp = G.rp.p;
+    sa.oci = st.oci = G.ci.p;
+    sa.cursor = st.cursor = cursor.p;
+    pass(true);
+    launch_iluk_sort_rows(n, G.rp.p, G.ci.p, mr, fail.p, c.st);
+    launch_iluk_scatter(n, F.rp.p, F.ci.p, F.val.p, G.rp.p, G.ci.p, G.val.p, fail.p, c.st);
+    HIPCHK(hipGetLastError());
+    if (const int32_t h = failed())
+        throw Error(who + ": inconsistent filled pattern (code " + std::to_string(h) + ")");
+    F.rp = std::move(G.rp);
+    F.ci = std::move(G.ci);
+    F.val = std::move(G.val);
+    F.nnz = fnnz;
+    F.max_row = mr;
 }
 
 PCILU::PCILU(const DevCSR &M, int64_t nb, Ctx &c, const Config &cfg) {
@@ -862,13 +998,20 @@ PCILU::PCILU(const DevCSR &M, int64_t nb, Ctx &c, const Config &cfg) {
     lds_rr = cfg.rr && block_sweep_not_ring();
     profile_tag = cfg.profile_tag;
     const bool windows = sweep == Sweep::Window || sweep == Sweep::WindowRing || sweep == Sweep::LevelsWindowRing;
-    if (c.ilu_view)
-        fprintf(stderr, "[pls ilu] type %s n %lld blocks %lld max_len %lld levels %lld/%lld sweep %s%s\n", type.c_str(),
+    if (c.ilu_view) {
+        // levels of fill: appended where the option is set (the recorded ILU(0) lines stay as they are)
+        char fill[96] = "";
+        if (levels > 0)
+            snprintf(fill, sizeof(fill), " levels %d fill %.3f (rows through global memory %lld)", levels,
+                     nnz_block ? (double)F.nnz / (double)nnz_block : 1.0, (long long)iluk_gmem_rows);
+        fprintf(stderr, "[pls ilu] type %s n %lld blocks %lld max_len %lld levels %lld/%lld sweep %s%s%s\n", type.c_str(),
                 (long long)n, (long long)nblocks, (long long)max_len, (long long)nlev_L, (long long)nlev_U,
                 sweep_kind(),
                 windows ? (" (records " + std::to_string(window_records(window_entries_L)) + "/" +
                            std::to_string(window_records(window_entries_U)) + ")").c_str()
-                        : "");
+                        : "",
+                fill);
+    }
 }
 
 // Extract the block-Jacobi truncation (or the envelope) of M, find its
@@ -909,6 +1052,16 @@ void PCILU::factor(const DevCSR &M, int64_t nb, Ctx &c, const Config &cfg, Setup
     }
     if (exact) envelope_csr(M, F, c);
     else extract_csr(M, 0, n, w, 0, n, F, c);
+    nnz_block = F.nnz;
+    levels = (!exact && !sgs) ? cfg.levels : 0;
+    if (levels > 0) {
+        const auto t0 = std::chrono::steady_clock::now();
+        fill_levels(c, cfg);
+        if (std::getenv("PLS_ILU_TRACE"))  // (fill_levels ends synchronised)
+            fprintf(stderr, "[pcilu n %lld] symbolic ILU(%d) + values %.3f s, fill %.3f, rows through global memory %lld\n",
+                    (long long)n, levels, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(),
+                    nnz_block ? (double)F.nnz / (double)nnz_block : 1.0, (long long)iluk_gmem_rows);
+    }
     if (F.max_row > ilu0_max_row()) throw Error("ILU(0): row too long for the LDS-staged factorization");
     diag.alloc(std::max<int64_t>(n, 1));
     dinv.alloc(std::max<int64_t>(n, 1));

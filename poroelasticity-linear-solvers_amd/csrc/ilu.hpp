@@ -104,10 +104,18 @@ struct PCILU : PC {
         int lds_depth = 2;        // levels of factor data in flight in the LDS sweep (pls.sweep_depth 2 / 3 / 4)
         bool rr = false;          // round-robin level sweep (deep DAGs of ~one slice per level; pls.sweep_rr)
         std::string profile_tag;  // non-empty: dump per-block sweep timings once (pls.sweep_profile)
+        // levels of fill (<prefix>pc_factor_levels, <prefix>sub_pc_factor_levels for bjacobi's blocks): the
+        // ILU(k) pattern of the truncated block replaces the block's own before the factorization (iluk.hip)
+        int levels = 0;
+        std::string levels_key;  // the option that set it (error messages)
+        // test knob (pls.iluk_lds_slots): hash table slots of a symbolic search in LDS, a power of two
+        // in [256, 8192]; 0: by the block's longest row.  Rows that need more go through global memory
+        int iluk_lds_slots = 0;
         // pls.ilu_lds, pls.ilu_gmem and pls.ilu_ring, and of the sweep tuning options those
         // a site honours (reads): pls.sweep_tpb and pls.sweep_rr (Tuning), pls.sweep_depth /
         // <prefix>pls_sweep_depth (Depth), pls.sweep_lpr and pls.sweep_profile (LprProfile)
-        enum Reads : unsigned { Tuning = 1, Depth = 2, LprProfile = 4 };
+        // Levels / SubLevels: the levels of fill of an ilu / of bjacobi's blocks
+        enum Reads : unsigned { Tuning = 1, Depth = 2, LprProfile = 4, Levels = 8, SubLevels = 16 };
         static Config from_options(const Options &o, const std::string &prefix, unsigned reads);
     };
     PCILU(const DevCSR &M, int64_t nblocks, Ctx &c, const Config &cfg);
@@ -129,6 +137,10 @@ struct PCILU : PC {
     Sweep sweep = Sweep::Levels;
     int64_t nblocks = 1, max_len = 0, nlev_L = 0, nlev_U = 0;  // max_len: longest block
     bool exact = false, sgs = false;  // Config::exact_lu, Config::sgs
+    // Config::levels where it applies, the truncated block's entries before the fill (after: F.nnz,
+    // longest row F.max_row), rows whose symbolic search left LDS (pls_get_ilu_fill, pls.ilu_view)
+    int levels = 0;
+    int64_t nnz_block = 0, iluk_gmem_rows = 0;
     std::vector<int64_t> bstart_h;    // Config::bounds (empty: PETSc's bjacobi sizes)
     DBuf<int64_t> bstart;
     DevCSR F;  // truncated matrix, factored in place
@@ -153,6 +165,7 @@ struct PCILU : PC {
     DBuf<int64_t> wstart;  // windows and super-windows: per block its first window
     SwinTri Lsw, Usw;      // Swin
 
+    void fill_levels(Ctx &c, const Config &cfg);  // F <- its ILU(levels) pattern, zeros in the new places
     struct Setup;  // the constructor's steps share a host copy of the factors' pattern and the level orders
     void factor(const DevCSR &M, int64_t nb, Ctx &c, const Config &cfg, Setup &s);
     Sweep choose_sweep(Setup &s, const Ctx &c, const Config &cfg) const;

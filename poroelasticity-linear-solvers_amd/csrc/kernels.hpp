@@ -174,6 +174,35 @@ void launch_ilu0_dep(int64_t n, const int32_t *rows, const int64_t *rp, const in
 void set_ilu0_test_caps(int stage_cap, int grid_cap);
 void launch_find_diag(int64_t n, const int64_t *rp, const int32_t *ci, int64_t *diag, int32_t *fail,
                       hipStream_t st);
+// ILU(k) symbolic phase (iluk.hip): the pattern of the levels-of-fill factorization from one
+// breadth-first search per row of G(A) (U parts) and of G(A^T) (L parts, by columns).
+struct IlukSearch {
+    int64_t n;          // searches of the whole launch: rows 0 .. n - 1
+    const int64_t *rp;  // the graph searched: the block's pattern, or its transpose (rows need not be sorted)
+    const int32_t *ci;
+    int levels;      // k >= 1
+    int slot_bits;   // log2 of a search's hash table slots
+    int transposed;  // 0: entries (i, t) of the search from i; 1: entries (t, i)
+    int32_t *lcnt, *ucnt;  // entries left / right of the diagonal per row (the count pass writes them)
+    int32_t *ovf_rows, *ovf_n;  // count pass: the rows whose search outgrew its LDS table
+    const int64_t *orp;  // fill pass: the filled pattern's row pointers, columns (unsorted), L cursors
+    int32_t *oci, *cursor;
+    int32_t *fail;  // |= 1: a search outgrew the global-memory table too
+};
+int64_t iluk_search_table_ints(int slots);  // ints of one search's table and queue
+// the transposed pattern: column counts (cnt: n + 1 zeroed entries), then the columns (cursor: n zeroed)
+void launch_iluk_transpose_count(int64_t n, const int64_t *rp, const int32_t *ci, int64_t *cnt, hipStream_t st);
+void launch_iluk_transpose_fill(int64_t n, const int64_t *rp, const int32_t *ci, const int64_t *trp, int32_t *cursor,
+                                int32_t *tci, hipStream_t st);
+// every row with tables in LDS; then the listed rows with tables in global memory (gtab: grid tables)
+void launch_iluk_search(const IlukSearch &a, bool fill, hipStream_t st);
+void launch_iluk_search_gmem(const IlukSearch &a, bool fill, int64_t nlist, int grid, int *gtab, hipStream_t st);
+void launch_iluk_row_len(int64_t n, const int32_t *lcnt, const int32_t *ucnt, int64_t *len, hipStream_t st);
+// sort every row's columns ascending (fail |= 2: a duplicate column)
+void launch_iluk_sort_rows(int64_t n, const int64_t *rp, int32_t *ci, int64_t max_row, int32_t *fail, hipStream_t st);
+// the block's values into the filled pattern (dval zeroed; fail |= 4: an entry without a place)
+void launch_iluk_scatter(int64_t n, const int64_t *srp, const int32_t *sci, const double *sval, const int64_t *drp,
+                         const int32_t *dci, double *dval, int32_t *fail, hipStream_t st);
 // Symmetric Gauss-Seidel "factors" in ILU(0) storage (hypre relax type 6 as a
 // preconditioner M = (D + L) D^-1 (D + U)): strict-lower entries scaled by the
 // column's 1/a_jj (the unit lower factor I + L D^-1), diagonal and upper kept

@@ -1304,6 +1304,7 @@ struct PCRedundant : PC {
         launch_gather(nloc, mine.p, yg.p, y, c.st);
     }
     bool holds_ksp() const override { return inner->holds_ksp(); }
+    const PC *unwrapped() const override { return inner->unwrapped(); }
 };
 
 std::unique_ptr<PC> make_redundant(const std::string &type, const DevCSR &M, Ctx &c,
@@ -1341,10 +1342,8 @@ std::unique_ptr<PC> make_pc(const std::string &type, const DevCSR &M, const Opti
                               prefix, gathered ? &pre : nullptr);
     }
     if (type == "ilu") {
-        if (o.integer(prefix + "pc_factor_levels", 0) != 0)
-            throw Error(prefix + "pc_factor_levels > 0: only ILU(0) is implemented");
         using Cfg = PCILU::Config;
-        return std::make_unique<PCILU>(M, 1, c, Cfg::from_options(o, prefix, Cfg::Tuning | Cfg::Depth));
+        return std::make_unique<PCILU>(M, 1, c, Cfg::from_options(o, prefix, Cfg::Tuning | Cfg::Depth | Cfg::Levels));
     }
     if (type == "lu" || type == "cholesky") return make_lu(M, o, c);
     if (type == "bjacobi") {
@@ -1355,11 +1354,9 @@ std::unique_ptr<PC> make_pc(const std::string &type, const DevCSR &M, const Opti
         if (dist) nb = std::max<int64_t>(1, nbt / c.comm->size + (c.comm->rank < nbt % c.comm->size ? 1 : 0));
         const std::string sub = o.str(prefix + "sub_pc_type", "ilu");
         if (sub == "ilu") {
-            if (o.integer(prefix + "sub_pc_factor_levels", 0) != 0)
-                throw Error(prefix + "sub_pc_factor_levels > 0: only ILU(0) is implemented");
             using Cfg = PCILU::Config;
-            return std::make_unique<PCILU>(M, nb, c,
-                                           Cfg::from_options(o, prefix, Cfg::Tuning | Cfg::Depth | Cfg::LprProfile));
+            return std::make_unique<PCILU>(
+                M, nb, c, Cfg::from_options(o, prefix, Cfg::Tuning | Cfg::Depth | Cfg::LprProfile | Cfg::SubLevels));
         }
         if (sub == "jacobi") return std::make_unique<PCJacobi>(M, c);
         if (sub == "none") return std::make_unique<PCNone>(M.nrows);

@@ -364,6 +364,8 @@ struct PC {
     virtual bool holds_ksp() const { return false; }
     // the coupling product that belongs to the y apply() returned last (null: none)
     virtual Coupling *coupling_product() const { return nullptr; }
+    // the PC that does the work (a redundant PC: the one applied on the gathered block)
+    virtual const PC *unwrapped() const { return this; }
 };
 struct PCNone : PC {
     explicit PCNone(int64_t n_) { type = "none"; n = n_; }

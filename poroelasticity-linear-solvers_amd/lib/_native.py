@@ -48,7 +48,7 @@ EXPORTS = [
     "pls_bench_copy", "pls_create_dist", "pls_bench_global_sum", "pls_anderson_create",
     "pls_anderson_next", "pls_anderson_destroy", "pls_boomeramg_host_level", "pls_sparse_lu_analyze",
     "pls_get_ksp_stats", "pls_get_gmres_orthog_stats", "pls_get_chebyshev_bounds",
-    "pls_hessenberg_eigenvalues", "pls_get_reuse_stats",
+    "pls_hessenberg_eigenvalues", "pls_get_reuse_stats", "pls_get_ilu_fill",
 ]
 
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p)
@@ -91,6 +91,7 @@ def lib():
     L.pls_get_ksp_stats.argtypes = [vp, C.c_char_p, vp]
     L.pls_get_gmres_orthog_stats.argtypes = [vp, C.c_char_p, vp]
     L.pls_get_chebyshev_bounds.argtypes = [vp, C.c_char_p, vp]
+    L.pls_get_ilu_fill.argtypes = [vp, C.c_char_p, vp]
     L.pls_get_reuse_stats.argtypes = [vp, vp]
     L.pls_hessenberg_eigenvalues.argtypes = [C.c_int, vp, C.c_int, vp, vp]
     L.pls_export_matrix.argtypes = [vp, C.c_int, C.POINTER(i64), C.POINTER(i64), vp, vp, vp]

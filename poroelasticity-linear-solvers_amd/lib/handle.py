@@ -242,6 +242,13 @@ class Handle:
         N.check(N.lib().pls_get_chebyshev_bounds(self.ptr, prefix.encode(), N.ptr(s)))
         return tuple(float(v) for v in s)
 
+    def ilu_fill(self, prefix):
+        """(levels of fill, entries of the block-truncated matrix before the fill, after it, the
+        longest filled row) of the ilu / bjacobi(ilu) PC with this options prefix (pls_get_ilu_fill)."""
+        s = np.zeros(4, dtype=np.int64)
+        N.check(N.lib().pls_get_ilu_fill(self.ptr, prefix.encode(), N.ptr(s)))
+        return tuple(int(v) for v in s)
+
     def reuse_stats(self):
         """(reduced outer products, full outer products since the last reset_timings, eligible 0/1)
         of the coupling reuse (pls_get_reuse_stats)."""
