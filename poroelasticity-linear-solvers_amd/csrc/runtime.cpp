@@ -394,8 +394,13 @@ static std::vector<int32_t> rcm_order(const hvec<int64_t> &rp, const hvec<int32_
         for (int32_t v : q) lev[v] = -1;
         return last;
     };
-    for (int64_t s0 = 0; s0 < n; ++s0) {
-        if (done[s0]) continue;
+    for (int64_t s0 = 0; s0 < n;) {
+        // s0 again until it is ordered: in a pattern that is not symmetric the sweep can end in
+        // vertices s0 reaches that do not reach s0 back
+        if (done[s0]) {
+            ++s0;
+            continue;
+        }
         int32_t s = bfs_last(bfs_last((int32_t)s0));
         size_t h = order.size();
         order.push_back(s);
