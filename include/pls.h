@@ -224,6 +224,14 @@ int pls_get_ksp_stats(pls_handle *h, const char *prefix, int64_t stats[5]);
  * 2 refine_always, 3 modified Gram-Schmidt).  An unknown prefix or a KSP of
  * another type is an error.                                                 */
 int pls_get_gmres_orthog_stats(pls_handle *h, const char *prefix, int64_t stats[3]);
+/* The Krylov basis of the gmres / fgmres KSP with this prefix
+ * (<prefix>pls_gmres_basis): stats[0] its precision (0 double, 1 single),
+ * [1] bytes of the basis allocation, and since setup [2] cycles ended because
+ * the estimate had fallen by <prefix>pls_gmres_basis_drop, [3] converged
+ * estimates confirmed against the true residual at the next cycle start,
+ * [4] confirmations that failed and led to another cycle ([2]-[4] stay 0 with
+ * a double basis).  An unknown prefix or a KSP of another type is an error.  */
+int pls_get_gmres_basis_stats(pls_handle *h, const char *prefix, int64_t stats[5]);
 /* Coupling reuse (option pls.reuse_coupling): products with the outer operator
  * since the last pls_reset_timings, [0] reduced ones that continued the block
  * preconditioner's coupling product, [1] full ones; [2] 1 when the reduced

@@ -619,6 +619,19 @@ int pls_get_gmres_orthog_stats(pls_handle *hh, const char *prefix, int64_t *stat
         stats[2] = found->orthog;
     })
 }
+int pls_get_gmres_basis_stats(pls_handle *hh, const char *prefix, int64_t *stats) {
+    PLS_TRY({
+        const KSP *found = find_ksp(*reinterpret_cast<Handle *>(hh), prefix, stats, "pls_get_gmres_basis_stats");
+        if (found->type != "gmres" && found->type != "fgmres")
+            throw Error("pls_get_gmres_basis_stats: the solver with prefix '" + found->prefix + "' is of type " +
+                        found->type + ", not gmres or fgmres");
+        stats[0] = found->basis_single ? 1 : 0;
+        stats[1] = found->basis_bytes();
+        stats[2] = found->stat_cb_forced;
+        stats[3] = found->stat_cb_confirm;
+        stats[4] = found->stat_cb_failed;
+    })
+}
 int pls_get_chebyshev_bounds(pls_handle *hh, const char *prefix, double *out) {
     PLS_TRY({
         const KSP *found = find_ksp(*reinterpret_cast<Handle *>(hh), prefix, out, "pls_get_chebyshev_bounds");

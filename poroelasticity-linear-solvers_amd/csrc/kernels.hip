@@ -1280,6 +1280,296 @@ void launch_lincomb(int64_t n, int k, const double *V, int64_t ldv, const double
     if (n > 0) k_lincomb<<<stream_grid(n), TPB, 0, st>>>(n, k, V, ldv, c_dev, y);
 }
 
+// ------------------------------------------ compressed-basis GMRES (fp32 V) --
+// The counterparts of k_mdot / k_maxpy_norm / k_mgs_step / k_lincomb for a
+// Krylov basis stored in fp32 (pls_gmres_basis single): the columns are read as
+// floats and promoted, w and every sum stay fp64.  The data path is the double
+// kernels': 16-B loads -- four rows of a column per lane, two loads for the
+// matching rows of w -- chunks that start on multiples of 4 rows (columns are
+// 512-B aligned: ldv a multiple of 128 floats), two trips of loads issued ahead
+// of their FMAs, each lane summing its rows in ascending order, one partial per
+// (column, block) for k_final.  The n mod 4 tail rows of the last chunk are
+// thread 0's, after its vector rows, as the odd row is in the double kernels.
+typedef float cb_f4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ void chunk_quad(int64_t n, int nb, int b, int64_t &s, int64_t &e) {
+    int64_t c = (n + nb - 1) / nb;
+    c = (c + 3) & ~(int64_t)3;
+    s = (int64_t)b * c;
+    e = s + c;
+    if (e > n) e = n;
+    if (s > n) s = n;
+}
+__device__ __forceinline__ cb_f4 cb_ld(const float *p) { return *reinterpret_cast<const cb_f4 *>(p); }
+__device__ __forceinline__ cgs_d2 cb_ld2(const double *p) { return *reinterpret_cast<const cgs_d2 *>(p); }
+// a += v . w over four rows, ascending
+__device__ __forceinline__ void cb_dot4(double &a, const cb_f4 v, const cgs_d2 w0, const cgs_d2 w1) {
+    a += (double)v.x * w0.x;
+    a += (double)v.y * w0.y;
+    a += (double)v.z * w1.x;
+    a += (double)v.w * w1.y;
+}
+// t -= h v over four rows
+__device__ __forceinline__ void cb_sub4(cgs_d2 &t0, cgs_d2 &t1, double h, const cb_f4 v) {
+    t0.x -= h * (double)v.x;
+    t0.y -= h * (double)v.y;
+    t1.x -= h * (double)v.z;
+    t1.y -= h * (double)v.w;
+}
+
+__global__ __launch_bounds__(TPB) void k_mdot_f32(int64_t n, int k, const float *__restrict__ V, int64_t ldv,
+                                                  const double *__restrict__ w, double *partial) {
+    __shared__ double lds[TPB / 64];
+    const int nb = gridDim.x;
+    int64_t s, e;
+    chunk_quad(n, nb, blockIdx.x, s, e);
+    const int j0 = blockIdx.y * MDOT_NJ;
+    const int nj = (k - j0) < MDOT_NJ ? (k - j0) : MDOT_NJ;
+    double a[MDOT_NJ];
+#pragma unroll
+    for (int u = 0; u < MDOT_NJ; ++u) a[u] = 0.0;
+    const float *v0 = V + (int64_t)j0 * ldv;
+    int64_t i = s + 4 * threadIdx.x;
+    for (; i + 4 * TPB + 3 < e; i += 8 * TPB) {
+        const cgs_d2 wa0 = cb_ld2(w + i), wa1 = cb_ld2(w + i + 2);
+        const cgs_d2 wb0 = cb_ld2(w + i + 4 * TPB), wb1 = cb_ld2(w + i + 4 * TPB + 2);
+        cb_f4 va[MDOT_NJ], vb[MDOT_NJ];
+#pragma unroll
+        for (int u = 0; u < MDOT_NJ; ++u) {
+            if (u < nj) {
+                va[u] = cb_ld(v0 + (int64_t)u * ldv + i);
+                vb[u] = cb_ld(v0 + (int64_t)u * ldv + i + 4 * TPB);
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < MDOT_NJ; ++u) {
+            if (u < nj) {
+                cb_dot4(a[u], va[u], wa0, wa1);
+                cb_dot4(a[u], vb[u], wb0, wb1);
+            }
+        }
+    }
+    for (; i + 3 < e; i += 4 * TPB) {
+        const cgs_d2 w0 = cb_ld2(w + i), w1 = cb_ld2(w + i + 2);
+#pragma unroll
+        for (int u = 0; u < MDOT_NJ; ++u)
+            if (u < nj) cb_dot4(a[u], cb_ld(v0 + (int64_t)u * ldv + i), w0, w1);
+    }
+    if (threadIdx.x == 0) {
+        for (int64_t l = e - ((e - s) & 3); l < e; ++l) {
+#pragma unroll
+            for (int u = 0; u < MDOT_NJ; ++u)
+                if (u < nj) a[u] += (double)v0[(int64_t)u * ldv + l] * w[l];
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < MDOT_NJ; ++u) {
+        if (u < nj) {
+            const double r = block_sum(a[u], lds);
+            if (threadIdx.x == 0) partial[(int64_t)(j0 + u) * nb + blockIdx.x] = r;
+        }
+    }
+}
+void launch_mdot_f32(int64_t n, int k, const float *V, int64_t ldv, const double *w, double *partial, double *out,
+                     hipStream_t st) {
+    if (k <= 0) return;
+    const int nb = reduce_blocks(n);
+    dim3 grid(nb, (k + MDOT_NJ - 1) / MDOT_NJ);
+    k_mdot_f32<<<grid, TPB, 0, st>>>(n, k, V, ldv, w, partial);
+    k_final<<<k, TPB, 0, st>>>(nb, partial, out, 0);
+}
+
+__global__ __launch_bounds__(TPB) void k_maxpy_norm_f32(int64_t n, int k, const float *__restrict__ V, int64_t ldv,
+                                                        const double *__restrict__ h, double *__restrict__ w,
+                                                        double *partial) {
+    __shared__ double lds[TPB / 64];
+    __shared__ double hs[512];
+    for (int j = threadIdx.x; j < k && j < 512; j += TPB) hs[j] = h[j];
+    __syncthreads();
+    int64_t s, e;
+    chunk_quad(n, gridDim.x, blockIdx.x, s, e);
+    double a = 0.0;
+    int64_t i = s + 4 * threadIdx.x;
+    for (; i + 4 * TPB + 3 < e; i += 8 * TPB) {
+        cgs_d2 ta0 = cb_ld2(w + i), ta1 = cb_ld2(w + i + 2);
+        cgs_d2 tb0 = cb_ld2(w + i + 4 * TPB), tb1 = cb_ld2(w + i + 4 * TPB + 2);
+        int j = 0;
+        for (; j + 8 <= k; j += 8) {
+            cb_f4 va[8], vb[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                va[u] = cb_ld(V + (int64_t)(j + u) * ldv + i);
+                vb[u] = cb_ld(V + (int64_t)(j + u) * ldv + i + 4 * TPB);
+            }
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                const double hj = (j + u) < 512 ? hs[j + u] : h[j + u];
+                cb_sub4(ta0, ta1, hj, va[u]);
+                cb_sub4(tb0, tb1, hj, vb[u]);
+            }
+        }
+        for (; j < k; ++j) {
+            const cb_f4 va = cb_ld(V + (int64_t)j * ldv + i);
+            const cb_f4 vb = cb_ld(V + (int64_t)j * ldv + i + 4 * TPB);
+            const double hj = j < 512 ? hs[j] : h[j];
+            cb_sub4(ta0, ta1, hj, va);
+            cb_sub4(tb0, tb1, hj, vb);
+        }
+        *reinterpret_cast<cgs_d2 *>(w + i) = ta0;
+        *reinterpret_cast<cgs_d2 *>(w + i + 2) = ta1;
+        *reinterpret_cast<cgs_d2 *>(w + i + 4 * TPB) = tb0;
+        *reinterpret_cast<cgs_d2 *>(w + i + 4 * TPB + 2) = tb1;
+        a += ta0.x * ta0.x;
+        a += ta0.y * ta0.y;
+        a += ta1.x * ta1.x;
+        a += ta1.y * ta1.y;
+        a += tb0.x * tb0.x;
+        a += tb0.y * tb0.y;
+        a += tb1.x * tb1.x;
+        a += tb1.y * tb1.y;
+    }
+    for (; i + 3 < e; i += 4 * TPB) {
+        cgs_d2 t0 = cb_ld2(w + i), t1 = cb_ld2(w + i + 2);
+        int j = 0;
+        for (; j + 8 <= k; j += 8) {
+            cb_f4 v[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) v[u] = cb_ld(V + (int64_t)(j + u) * ldv + i);
+#pragma unroll
+            for (int u = 0; u < 8; ++u) cb_sub4(t0, t1, (j + u) < 512 ? hs[j + u] : h[j + u], v[u]);
+        }
+        for (; j < k; ++j) cb_sub4(t0, t1, j < 512 ? hs[j] : h[j], cb_ld(V + (int64_t)j * ldv + i));
+        *reinterpret_cast<cgs_d2 *>(w + i) = t0;
+        *reinterpret_cast<cgs_d2 *>(w + i + 2) = t1;
+        a += t0.x * t0.x;
+        a += t0.y * t0.y;
+        a += t1.x * t1.x;
+        a += t1.y * t1.y;
+    }
+    if (threadIdx.x == 0) {
+        for (int64_t l = e - ((e - s) & 3); l < e; ++l) {
+            double t = w[l];
+            for (int j = 0; j < k; ++j) t -= (j < 512 ? hs[j] : h[j]) * (double)V[(int64_t)j * ldv + l];
+            w[l] = t;
+            a += t * t;
+        }
+    }
+    if (partial) {
+        a = block_sum(a, lds);
+        if (threadIdx.x == 0) partial[blockIdx.x] = a;
+    }
+}
+void launch_maxpy_norm_f32(int64_t n, int k, const float *V, int64_t ldv, const double *h_dev, double *w,
+                           double *partial, double *out, hipStream_t st) {
+    const int nb = reduce_blocks(n);
+    k_maxpy_norm_f32<<<nb, TPB, 0, st>>>(n, k, V, ldv, h_dev, w, out ? partial : nullptr);
+    if (out) k_final<<<1, TPB, 0, st>>>(nb, partial, out, 0);
+}
+
+// k_mgs_step over fp32 columns (no single-launch sums: k_final follows every step)
+__global__ __launch_bounds__(TPB) void k_mgs_step_f32(int64_t n, const float *__restrict__ vprev,
+                                                      const double *__restrict__ hprev, const float *__restrict__ vj,
+                                                      double *w, double *partial) {
+    __shared__ double lds[TPB / 64];
+    int64_t s, e;
+    chunk_quad(n, gridDim.x, blockIdx.x, s, e);
+    const double hp = vprev ? *hprev : 0.0;
+    double a = 0.0;
+    // four rows at i: the update by vprev, then their part of (w, vj) or (w, w)
+    auto quad = [&](int64_t i, cgs_d2 t0, cgs_d2 t1, const cb_f4 p, const cb_f4 v) {
+        if (vprev) {
+            cb_sub4(t0, t1, hp, p);
+            *reinterpret_cast<cgs_d2 *>(w + i) = t0;
+            *reinterpret_cast<cgs_d2 *>(w + i + 2) = t1;
+        }
+        if (vj) {
+            cb_dot4(a, v, t0, t1);
+        } else {
+            a += t0.x * t0.x;
+            a += t0.y * t0.y;
+            a += t1.x * t1.x;
+            a += t1.y * t1.y;
+        }
+    };
+    const cb_f4 zero = {0.f, 0.f, 0.f, 0.f};
+    int64_t i = s + 4 * threadIdx.x;
+    for (; i + 4 * TPB + 3 < e; i += 8 * TPB) {
+        const cgs_d2 ta0 = cb_ld2(w + i), ta1 = cb_ld2(w + i + 2);
+        const cgs_d2 tb0 = cb_ld2(w + i + 4 * TPB), tb1 = cb_ld2(w + i + 4 * TPB + 2);
+        cb_f4 pa = zero, pb = zero, va = zero, vb = zero;
+        if (vprev) {
+            pa = cb_ld(vprev + i);
+            pb = cb_ld(vprev + i + 4 * TPB);
+        }
+        if (vj) {
+            va = cb_ld(vj + i);
+            vb = cb_ld(vj + i + 4 * TPB);
+        }
+        quad(i, ta0, ta1, pa, va);
+        quad(i + 4 * TPB, tb0, tb1, pb, vb);
+    }
+    for (; i + 3 < e; i += 4 * TPB) {
+        const cgs_d2 t0 = cb_ld2(w + i), t1 = cb_ld2(w + i + 2);
+        quad(i, t0, t1, vprev ? cb_ld(vprev + i) : zero, vj ? cb_ld(vj + i) : zero);
+    }
+    if (threadIdx.x == 0) {
+        for (int64_t l = e - ((e - s) & 3); l < e; ++l) {
+            double t = w[l];
+            if (vprev) {
+                t -= hp * (double)vprev[l];
+                w[l] = t;
+            }
+            a += (vj ? (double)vj[l] : t) * t;
+        }
+    }
+    a = block_sum(a, lds);
+    if (threadIdx.x == 0) partial[blockIdx.x] = a;
+}
+void launch_mgs_step_f32(int64_t n, const float *vprev, const double *hprev, const float *vj, double *w,
+                         double *partial, hipStream_t st) {
+    k_mgs_step_f32<<<reduce_blocks(n), TPB, 0, st>>>(n, vprev, hprev, vj, w, partial);
+}
+
+__global__ __launch_bounds__(TPB) void k_lincomb_f32(int64_t n, int k, const float *__restrict__ V, int64_t ldv,
+                                                     const double *__restrict__ c, double *__restrict__ y) {
+    __shared__ double cs[512];
+    for (int j = threadIdx.x; j < k && j < 512; j += TPB) cs[j] = c[j];
+    __syncthreads();
+    for (int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x; i < n; i += (int64_t)gridDim.x * TPB) {
+        double t = 0.0;
+        for (int j = 0; j < k; ++j) t += (j < 512 ? cs[j] : c[j]) * (double)V[(int64_t)j * ldv + i];
+        y[i] = t;
+    }
+}
+void launch_lincomb_f32(int64_t n, int k, const float *V, int64_t ldv, const double *c_dev, double *y,
+                        hipStream_t st) {
+    if (n > 0) k_lincomb_f32<<<stream_grid(n), TPB, 0, st>>>(n, k, V, ldv, c_dev, y);
+}
+
+// The new basis vector: vf = fl32(a w) (round to nearest even) and vd = vf promoted, the
+// vector the next operator / PC application reads, in one pass over w.  Four rows per lane
+// (vf, vd and w 32-B aligned, n >= 0 rows; the n mod 4 tail rows one lane each).
+__global__ __launch_bounds__(TPB) void k_scale_round(int64_t n, double a, const double *__restrict__ w,
+                                                     float *__restrict__ vf, double *__restrict__ vd) {
+    const int64_t nq = n >> 2, tid = (int64_t)blockIdx.x * TPB + threadIdx.x, stride = (int64_t)gridDim.x * TPB;
+    for (int64_t q = tid; q < nq; q += stride) {
+        const int64_t i = 4 * q;
+        const cgs_d2 w0 = cb_ld2(w + i), w1 = cb_ld2(w + i + 2);
+        const cb_f4 f = {(float)(w0.x * a), (float)(w0.y * a), (float)(w1.x * a), (float)(w1.y * a)};
+        *reinterpret_cast<cb_f4 *>(vf + i) = f;
+        *reinterpret_cast<cgs_d2 *>(vd + i) = cgs_d2{(double)f.x, (double)f.y};
+        *reinterpret_cast<cgs_d2 *>(vd + i + 2) = cgs_d2{(double)f.z, (double)f.w};
+    }
+    const int64_t l = 4 * nq + tid;
+    if (l < n) {
+        const float f = (float)(w[l] * a);
+        vf[l] = f;
+        vd[l] = (double)f;
+    }
+}
+void launch_scale_round(int64_t n, double a, const double *w, float *vf, double *vd, hipStream_t st) {
+    if (n > 0) k_scale_round<<<stream_grid((n + 3) / 4), TPB, 0, st>>>(n, a, w, vf, vd);
+}
+
 // TSQR leaf / tree step for the Anderson least squares (numpy Householder QR
 // in the reference, lib/AAR.py:102-105): workgroup b takes rows
 // [b C, b C + C) of the m <= 16 columns cols[k] (rows >= n read as zero),

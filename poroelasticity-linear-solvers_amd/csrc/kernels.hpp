@@ -151,6 +151,19 @@ void launch_mgs_step(int64_t n, const double *vprev, const double *hprev, const 
 // y = sum_j c[j] * V[:, j] (c on device)
 void launch_lincomb(int64_t n, int k, const double *V, int64_t ldv, const double *c_dev, double *y,
                     hipStream_t st);
+// Compressed-basis GMRES (pls_gmres_basis single): the same four over a basis stored in fp32
+// (ldv a multiple of 128 floats), w and all sums fp64 ...
+void launch_mdot_f32(int64_t n, int k, const float *V, int64_t ldv, const double *w, double *partial, double *out,
+                     hipStream_t st);
+void launch_maxpy_norm_f32(int64_t n, int k, const float *V, int64_t ldv, const double *h_dev, double *w,
+                           double *partial, double *out, hipStream_t st);
+// (one partial per block into partial; the caller runs launch_final)
+void launch_mgs_step_f32(int64_t n, const float *vprev, const double *hprev, const float *vj, double *w,
+                         double *partial, hipStream_t st);
+void launch_lincomb_f32(int64_t n, int k, const float *V, int64_t ldv, const double *c_dev, double *y,
+                        hipStream_t st);
+// ... and the new basis vector: vf = fl32(a w), vd = vf promoted to fp64, one pass
+void launch_scale_round(int64_t n, double a, const double *w, float *vf, double *vd, hipStream_t st);
 // TSQR step (Anderson least squares): R of each TSQR rows-per-block row chunk of the
 // m <= 16 columns, written as rows [b m, b m + m) of a column-major matrix (leading dim ldo)
 int tsqr_rows_per_block();

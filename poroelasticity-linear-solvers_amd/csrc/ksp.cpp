@@ -94,6 +94,28 @@ void KSP::ensure_work(Ctx &c) {
         // (the context's default room, 136 columns at the largest grid, overflowed
         // past ~450 iterations of a 1.3M-row solve)
         c.ensure_partial(n, restart + 2);
+        if (allocated_single != (int)basis_single) {  // the basis mode changed: nothing allocated fits
+            allocated_single = (int)basis_single;
+            allocated_k = -1;
+            V.release();
+            Vf.release();
+            cbw.release();
+            cbv.release();
+        }
+        if (basis_single && allocated_k != restart) {
+            ldv = (n + 127) & ~(int64_t)127;  // 512-B aligned columns of floats; Z, fp64, has the same stride
+            vf_canary = c.debug_bounds;
+            Vf.alloc((size_t)(restart + 1) * ldv + (vf_canary ? Ctx::CANARY : 0));
+            if (vf_canary)
+                HIPCHK(hipMemsetAsync(Vf.p + (size_t)(restart + 1) * ldv, 0xA5, sizeof(float) * Ctx::CANARY, c.st));
+            cbw.alloc(std::max<int64_t>(n, 1));
+            cbv.alloc(std::max<int64_t>(n, 1));
+            if (type == "fgmres") Z.alloc((size_t)restart * ldv);
+            else t1.alloc(n);
+            t2.alloc(n);
+            dh.alloc(2 * restart + 4);
+            allocated_k = restart;
+        }
         if (allocated_k != restart) {
             ldv = (n + 63) & ~(int64_t)63;  // 512-B aligned columns (16-B loads), V and Z alike
             V.alloc((size_t)(restart + 1) * ldv);
@@ -168,7 +190,8 @@ void KSP::solve(const double *b, double *x, Ctx &c) {
         reason = CONVERGED_ITS;
     } else {
         ensure_work(c);
-        if (type == "gmres" || type == "fgmres") solve_gmres(b, x, c);
+        if ((type == "gmres" || type == "fgmres") && basis_single) solve_gmres_cb(b, x, c);
+        else if (type == "gmres" || type == "fgmres") solve_gmres(b, x, c);
         else if (type == "richardson") solve_richardson(b, x, c);
         else if (type == "chebyshev") solve_chebyshev(b, x, c);
         else if (type == "cg") device_loop_allowed() ? solve_cg_dev(b, x, c) : solve_cg(b, x, c);
@@ -180,6 +203,19 @@ void KSP::solve(const double *b, double *x, Ctx &c) {
     stat_div += reason < 0 ? 1 : 0;
     if (reason < 0) stat_last_neg = reason;
     c.check_bounds();
+    if (vf_canary) check_basis_bounds(c);
+}
+
+// pls.debug_bounds: the guard bytes behind the fp32 basis, as Ctx::check_bounds checks those behind the partials
+void KSP::check_basis_bounds(Ctx &c) {
+    if (!Vf.p || Vf.n < (size_t)Ctx::CANARY) return;
+    std::vector<unsigned char> g(sizeof(float) * Ctx::CANARY);
+    HIPCHK(hipMemcpyAsync(g.data(), Vf.p + (Vf.n - Ctx::CANARY), g.size(), hipMemcpyDeviceToHost, c.st));
+    c.sync();
+    for (size_t i = 0; i < g.size(); ++i)
+        if (g[i] != 0xA5)
+            throw Error("pls.debug_bounds: the canary behind the fp32 Krylov basis (" + prefix +
+                        ") was overwritten at byte +" + std::to_string(i));
 }
 
 KSP::~KSP() {
@@ -354,6 +390,198 @@ double KSP::gmres_orthogonalise(int k, double *w, double *h, Ctx &c) {
         launch_mdot(n, k, nullptr, V.p, ldv, w, c.partials(n, k), d, c.st);
         c.comm->global_sum_dev(d, k, c.st);
         launch_maxpy_norm(n, k, V.p, ldv, d, -1.0, w, c.partials(n, 1), d + k, c.st);
+        c.comm->global_sum_dev(d + k, 1, c.st);
+        read_back(d);
+    };
+    cgs_pass(dh.p);
+    std::copy(hs, hs + k, h);
+    bool again = orthog == CGS_ALWAYS;
+    if (orthog == CGS_IFNEEDED) {
+        double hh = 0.0;
+        for (int j = 0; j < k; ++j) hh += h[j] * h[j];
+        again = std::sqrt(hs[k]) < std::sqrt(hh);
+    }
+    if (again) {
+        ++stat_orth_second;
+        cgs_pass(dh.p + k + 1);
+        for (int j = 0; j < k; ++j) h[j] += hs[j];
+    }
+    return hs[k];
+}
+
+// ------------------------------------------------- compressed-basis GMRES --
+// solve_gmres over a basis stored in fp32 (<prefix>pls_gmres_basis single; Aliaga, Anzt et al.,
+// "Compressed basis GMRES").  Every basis vector is rounded once, v = fl32(w / ||w||), and the
+// operator and the PC are applied to the promoted rounded vector (cbv), so the Arnoldi relation
+// holds for the basis that is stored; w (cbw), every sum and the Hessenberg matrix stay fp64.
+// One cycle cannot reduce the residual by much more than fp32's unit roundoff, and its Givens
+// estimate drifts from the true residual by then, hence two rules (norm type not none):
+//   (a) the cycle ends once the estimate is <= basis_drop x the residual the cycle began with;
+//   (b) a positive reason from the estimate ends the cycle, not the solve: x is built, the next
+//       cycle start computes and records the true residual at the same its, and that value
+//       decides -- at its == max_it too, where a failed check is DIVERGED_ITS.
+// A forced or confirming cycle start appends one history entry, as any restart does.  With norm
+// type none nothing is recorded or tested: max_it steps, CONVERGED_ITS.
+void KSP::solve_gmres_cb(const double *b, double *x, Ctx &c) {
+    const bool flexible = type == "fgmres", normed = norm != "none";
+    const int64_t mk = restart;
+    const double haptol = 1e-30;
+    std::vector<double> HH((mk + 1) * (mk + 1), 0.0), cc(mk + 1, 0.0), ss(mk + 1, 0.0), grs(mk + 2, 0.0),
+        nrs(mk + 1, 0.0), hcol(mk + 1, 0.0);
+    auto H = [&](int64_t i, int64_t j) -> double & { return HH[(size_t)i * (mk + 1) + j]; };
+    double *w = cbw.p, *vd = cbv.p, *t1p = t1.p, *t2p = t2.p;
+    launch_set(n, 0.0, x, c.st);
+    its = 0;
+    reason = 0;
+    bool first = true, confirming = false;
+    while (true) {
+        if (first) {
+            launch_copy(n, b, right ? w : t1p, c.st);
+        } else {
+            A->apply(x, t2p, c);
+            launch_waxpby(n, 1.0, b, -1.0, t2p, right ? w : t1p, c.st);
+        }
+        if (!right) pc->apply(t1p, w, c);
+        double res = c.norm2(n, w);
+        if (normed) {
+            reason = record(its, res);
+            if (confirming) {
+                ++stat_cb_confirm;
+                if (!reason) ++stat_cb_failed;
+            }
+        }
+        confirming = false;
+        if (res == 0.0) {
+            reason = CONVERGED_ATOL;
+            break;
+        }
+        if (reason) break;
+        if (its >= maxit) {  // (a confirmation that failed at max_it, or max_it 0)
+            reason = normed ? DIVERGED_ITS : CONVERGED_ITS;
+            break;
+        }
+        const double res0c = res;
+        launch_scale_round(n, 1.0 / res, w, Vf.p, vd, c.st);
+        std::fill(HH.begin(), HH.end(), 0.0);
+        grs.assign(mk + 2, 0.0);
+        grs[0] = res;
+        int64_t loc_it = 0;
+        int creason = 0;  // the cycle's reason, from its estimates
+        bool forced = false;
+        while (!creason && !forced && loc_it < mk && its < maxit) {
+            if (right) {
+                double *zk = flexible ? Z.p + loc_it * ldv : t1p;
+                pc->apply(vd, zk, c);
+                A->apply_after(*pc, zk, w, c);
+            } else {
+                A->apply(vd, t1p, c);
+                pc->apply(t1p, w, c);
+            }
+            const int k = (int)(loc_it + 1);
+            const double tt = std::sqrt(gmres_orthogonalise_cb(k, w, hcol.data(), c));
+            for (int j = 0; j < k; ++j) H(j, loc_it) = hcol[j];
+            H(loc_it + 1, loc_it) = tt;
+            double hapbnd = std::fabs(tt / grs[loc_it]);
+            if (hapbnd > haptol) hapbnd = haptol;
+            const bool hapend = tt < hapbnd;
+            if (!hapend) launch_scale_round(n, 1.0 / tt, w, Vf.p + (loc_it + 1) * ldv, vd, c.st);
+            // KSPGMRESUpdateHessenberg
+            const int64_t it = loc_it;
+            for (int64_t j = 0; j < it; ++j) {
+                const double t0 = H(j, it);
+                H(j, it) = cc[j] * t0 + ss[j] * H(j + 1, it);
+                H(j + 1, it) = cc[j] * H(j + 1, it) - ss[j] * t0;
+            }
+            if (!hapend) {
+                const double t0 = std::sqrt(H(it, it) * H(it, it) + H(it + 1, it) * H(it + 1, it));
+                if (t0 == 0.0) {
+                    creason = DIVERGED_NULL;
+                    break;
+                }
+                cc[it] = H(it, it) / t0;
+                ss[it] = H(it + 1, it) / t0;
+                grs[it + 1] = -(ss[it] * grs[it]);
+                grs[it] = cc[it] * grs[it];
+                H(it, it) = cc[it] * H(it, it) + ss[it] * H(it + 1, it);
+                res = std::fabs(grs[it + 1]);
+            } else {
+                res = 0.0;
+            }
+            loc_it++;
+            its++;
+            if (normed) creason = record(its, res);
+            if (hapend && !creason) {
+                creason = DIVERGED_BREAKDOWN;
+                break;
+            }
+            // rule (a), where the cycle would otherwise go on
+            forced = normed && !creason && basis_drop > 0.0 && res <= basis_drop * res0c && loc_it < mk && its < maxit;
+        }
+        // KSPGMRESBuildSoln: x += M^-1 V y (right), V y (left), Z y (fgmres; Z is fp64)
+        const int64_t it = loc_it - 1;
+        if (it >= 0) {
+            if (H(it, it) == 0.0) {
+                creason = DIVERGED_BREAKDOWN;
+            } else {
+                nrs[it] = grs[it] / H(it, it);
+                for (int64_t k = it - 1; k >= 0; --k) {
+                    double t0 = grs[k];
+                    for (int64_t j = k + 1; j <= it; ++j) t0 = t0 - H(k, j) * nrs[j];
+                    nrs[k] = t0 / H(k, k);
+                }
+                HIPCHK(hipMemcpyAsync(dh.p, nrs.data(), sizeof(double) * (it + 1), hipMemcpyHostToDevice, c.st));
+                if (flexible) launch_lincomb(n, (int)(it + 1), Z.p, ldv, dh.p, t2p, c.st);
+                else launch_lincomb_f32(n, (int)(it + 1), Vf.p, ldv, dh.p, t2p, c.st);
+                if (right && !flexible) {
+                    pc->apply(t2p, t1p, c);
+                    launch_axpby(n, 1.0, t1p, 1.0, x, c.st);
+                } else {
+                    launch_axpby(n, 1.0, t2p, 1.0, x, c.st);
+                }
+                c.sync();  // nrs host buffer reuse
+            }
+        }
+        first = false;
+        if (creason < 0) {
+            reason = creason;
+            break;
+        }
+        if (creason > 0) {  // rule (b)
+            confirming = true;
+            continue;
+        }
+        if (its >= maxit) {
+            reason = normed ? DIVERGED_ITS : CONVERGED_ITS;
+            break;
+        }
+        if (forced) ++stat_cb_forced;
+    }
+}
+
+// gmres_orthogonalise over the fp32 basis: the same passes and rules, the columns read as
+// floats by the _f32 kernels (k_final after every MGS step: no single-launch sums here).
+double KSP::gmres_orthogonalise_cb(int k, double *w, double *h, Ctx &c) {
+    double *hs = c.host_scalars(k + 1);
+    auto read_back = [&](const double *d) {
+        HIPCHK(hipMemcpyAsync(hs, d, sizeof(double) * (k + 1), hipMemcpyDeviceToHost, c.st));
+        c.sync();
+    };
+    ++stat_orth_steps;
+    if (orthog == MGS) {
+        for (int j = 0; j <= k; ++j) {
+            launch_mgs_step_f32(n, j > 0 ? Vf.p + (int64_t)(j - 1) * ldv : nullptr, j > 0 ? dh.p + (j - 1) : nullptr,
+                                j < k ? Vf.p + (int64_t)j * ldv : nullptr, w, mgs_part.p, c.st);
+            launch_final(n, 1, mgs_part.p, dh.p + j, c.st);
+            c.comm->global_sum_dev(dh.p + j, 1, c.st);
+        }
+        read_back(dh.p);
+        std::copy(hs, hs + k, h);
+        return hs[k];
+    }
+    auto cgs_pass = [&](double *d) {
+        launch_mdot_f32(n, k, Vf.p, ldv, w, c.partials(n, k), d, c.st);
+        c.comm->global_sum_dev(d, k, c.st);
+        launch_maxpy_norm_f32(n, k, Vf.p, ldv, d, w, c.partials(n, 1), d + k, c.st);
         c.comm->global_sum_dev(d + k, 1, c.st);
         read_back(d);
     };
@@ -943,6 +1171,18 @@ std::unique_ptr<KSP> make_ksp(const std::string &prefix, const Options &o, const
         else throw Error(key + ": unknown value '" + rt + "' (refine_never, refine_ifneeded, refine_always)");
         if (o.flag(prefix + "ksp_gmres_modifiedgramschmidt", false)) k->orthog = KSP::MGS;
         k->mgs_fused = o.flag("pls.gmres_mgs_fused", false);
+        // the precision the Krylov basis is stored in (other types ignore both options)
+        const std::string bkey = prefix + "pls_gmres_basis", basis = o.str(bkey, "double");
+        if (basis != "double" && basis != "single")
+            throw Error(bkey + ": unknown value '" + basis + "' (double, single)");
+        k->basis_single = basis == "single";
+        const std::string dkey = prefix + "pls_gmres_basis_drop";
+        k->basis_drop = o.num(dkey, 1e-6);
+        if (!(k->basis_drop >= 0.0 && k->basis_drop < 1.0))
+            throw Error(dkey + ": " + o.str(dkey, "") + " is outside 0 <= d < 1 (0 switches the rule off)");
+        if (k->basis_single && k->orthog == KSP::MGS && k->mgs_fused)
+            throw Error(bkey + " single is not available together with pls.gmres_mgs_fused 1 (" + prefix +
+                        "ksp_gmres_modifiedgramschmidt): the fp32 step kernel has no single-launch sums");
     }
     k->resolve_side_norm(o.str(prefix + "ksp_pc_side", ""), o.str(prefix + "ksp_norm_type", ""));
     k->poly_fuse_jacobi = o.flag("pls.poly_fuse_jacobi", true);

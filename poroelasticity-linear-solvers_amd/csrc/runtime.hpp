@@ -484,6 +484,19 @@ struct KSP {
     DBuf<double> mgs_part;       // MGS: one row of partials ...
     DBuf<unsigned> mgs_ticket;   // ... and the ticket of its single-launch reductions
     int64_t stat_orth_steps = 0, stat_orth_second = 0;  // Arnoldi steps orthogonalised, second CGS passes
+    // Compressed-basis GMRES (gmres, fgmres; <prefix>pls_gmres_basis single): the basis in fp32 (Vf, ldv a
+    // multiple of 128 floats), w (cbw) and the promoted newest basis vector (cbv), which the operator and the
+    // PC read, in fp64.  A cycle ends when the estimate has fallen by basis_drop from its start (rule a), and an
+    // estimate that meets the tolerance ends the cycle only: the next cycle's true residual decides (rule b).
+    bool basis_single = false;
+    double basis_drop = 1e-6;  // <prefix>pls_gmres_basis_drop (0: rule a off)
+    DBuf<float> Vf;
+    DBuf<double> cbw, cbv;
+    int allocated_single = -1;  // the mode the work vectors were allocated for
+    bool vf_canary = false;     // pls.debug_bounds: Ctx::CANARY guard bytes behind Vf (check_basis_bounds)
+    int64_t stat_cb_forced = 0, stat_cb_confirm = 0, stat_cb_failed = 0;  // rule (a) cycle ends, rule (b)
+                                                                          // confirmations, those that failed
+    int64_t basis_bytes() const { return basis_single ? (int64_t)(Vf.n * sizeof(float)) : (int64_t)(V.n * sizeof(double)); }
     // GMRES: keep the Hessenberg columns of the first cycle as Arnoldi made them (the cycle
     // rotates its own copy in place): hess[i + j * (restart + 1)], column j = step j
     bool keep_hess = false;
@@ -520,6 +533,10 @@ struct KSP {
     // one Arnoldi step: w orthogonalised against the first k columns of V; the Hessenberg
     // column's k entries into h (host), ||w||^2 returned
     double gmres_orthogonalise(int k, double *w, double *h, Ctx &c);
+    // the same cycle and step over the fp32 basis (basis_single)
+    void solve_gmres_cb(const double *b, double *x, Ctx &c);
+    double gmres_orthogonalise_cb(int k, double *w, double *h, Ctx &c);
+    void check_basis_bounds(Ctx &c);
     void solve_cg(const double *b, double *x, Ctx &c);
     void solve_cg_dev(const double *b, double *x, Ctx &c);
     void solve_bcgs(const double *b, double *x, Ctx &c);

@@ -234,6 +234,14 @@ class Handle:
         N.check(N.lib().pls_get_gmres_orthog_stats(self.ptr, prefix.encode(), N.ptr(s)))
         return tuple(int(v) for v in s)
 
+    def gmres_basis_stats(self, prefix):
+        """(basis precision: 0 double, 1 single; bytes of the basis allocation; cycles ended by the
+        drop rule; converged estimates confirmed against the true residual; confirmations that
+        failed) of the gmres / fgmres solver with this options prefix (pls_get_gmres_basis_stats)."""
+        s = np.zeros(5, dtype=np.int64)
+        N.check(N.lib().pls_get_gmres_basis_stats(self.ptr, prefix.encode(), N.ptr(s)))
+        return tuple(int(v) for v in s)
+
     def chebyshev_bounds(self, prefix):
         """(emin, emax as used, the estimate's smallest and largest real part -- NaN when the bounds
         were given explicitly) of the chebyshev solver with this options prefix, after its first
