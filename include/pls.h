@@ -176,7 +176,11 @@ int pls_setup(pls_handle *h);
  * solve -- PETSc's PCSetUp on an operator state change, which the reference
  * triggers every time step by re-applying BCs to A and P
  * (lib/Poromechanics.py:70-86, lib/Solver.py:105 set_up).  Outer solver,
- * AAR and inner Anderson histories persist, as the reference's objects do. */
+ * AAR and inner Anderson histories persist, as the reference's objects do;
+ * so does the outer solver's Fischer guess space (-global_ksp_guess_type
+ * fischer) unless A is non-NULL: a new A empties it and counts a reset
+ * (PETSc's operator-state check).  Inner solvers are built again, their
+ * guess spaces with them.                                                  */
 int pls_update_matrices(pls_handle *h, const pls_csr *A, const pls_csr *P, const pls_csr *P_diff);
 /* Set / override one option ("key", "value" or NULL for a flag).  Options of
  * the outer solver ("pls.solver_*", "pls.aar_*", "global_*") may change until
@@ -189,7 +193,10 @@ int pls_destroy(pls_handle *h);
 /* Global size n and field sizes of a handle.                                 */
 int pls_get_sizes(pls_handle *h, int64_t *n, int64_t *ns, int64_t *nf, int64_t *np, int64_t *nnz_A);
 
-/* Host-vector entry points (caller's ordering, length n).                     */
+/* Host-vector entry points (caller's ordering, length n).  pls_solve and
+ * pls_solve_device write x; they also read it, as the initial guess, when
+ * -global_ksp_initial_guess_nonzero is set and -global_ksp_guess_type is
+ * none -- and only then (a Fischer guess is formed from b alone).           */
 int pls_pc_apply(pls_handle *h, const double *x, double *y);
 int pls_solve(pls_handle *h, const double *b, double *x, pls_result *res);
 int pls_matmult(pls_handle *h, const double *x, double *y);
@@ -232,6 +239,28 @@ int pls_get_gmres_orthog_stats(pls_handle *h, const char *prefix, int64_t stats[
  * [4] confirmations that failed and led to another cycle ([2]-[4] stay 0 with
  * a double basis).  An unknown prefix or a KSP of another type is an error.  */
 int pls_get_gmres_basis_stats(pls_handle *h, const char *prefix, int64_t stats[5]);
+/* The initial guess of the KSP with this prefix (-<prefix>ksp_guess_type
+ * none|fischer, -<prefix>ksp_guess_fischer_model 2,<size>,
+ * -<prefix>ksp_guess_fischer_tol; -global_ksp_initial_guess_nonzero for the
+ * outer solver).  Fischer's model 2, the least-squares projection valid for a
+ * nonsymmetric operator, is the only model built and the default here
+ * (PETSc's default is model 1, which needs a symmetric operator).  stats[0]
+ * type (0 none, 1 fischer), [1] columns stored now, [2] size, and since setup
+ * [3] guesses formed, [4] updates skipped (the new direction was dependent),
+ * [5] resets (the space was full, or A changed).  *last_reduction:
+ * ||b - A x0|| / ||b|| of the most recent solve that started from a guess,
+ * NaN before the first and for b = 0 (where rnorm0 is the first residual's,
+ * as from a zero guess).  An unknown prefix is an error.                     */
+int pls_get_ksp_guess_stats(pls_handle *h, const char *prefix, int64_t stats[6], double *last_reduction);
+/* What the callers of pls_solve need to know about the KSP with this prefix,
+ * from the library's own reading of the options (the solver is created if it
+ * was not yet): *reads_x = 1 when x is an input of the solve -- the prefix is
+ * "global_", -global_ksp_initial_guess_nonzero is set and no Fischer guess
+ * replaces it -- else 0 (also with pls.solver_type aar); *seconds = HIP-event
+ * time the most recent solve spent on its guess (forming x0, r0 = b - A x0 and
+ * the norms before the zero-guess solve, x = x0 + d and the space's update
+ * after it) with pls.ksp_guess_timing 1, else NaN.                          */
+int pls_get_ksp_guess_info(pls_handle *h, const char *prefix, int64_t *reads_x, double *seconds);
 /* Coupling reuse (option pls.reuse_coupling): products with the outer operator
  * since the last pls_reset_timings, [0] reduced ones that continued the block
  * preconditioner's coupling product, [1] full ones; [2] 1 when the reduced

@@ -210,6 +210,12 @@ static void do_setup_solver(Handle &H) {
     H.Aop->coupling = &H.coupling;
     H.coupling_stale = true;
     if (H.solver_type == "aar") {
+        // AAR keeps its own start (x0 = None in the reference): the outer KSP's guess options have no meaning
+        for (const char *key : {"global_ksp_initial_guess_nonzero", "global_ksp_guess_type",
+                                "global_ksp_guess_fischer_model", "global_ksp_guess_fischer_tol"})
+            if (o.has(key))
+                throw Error(std::string(key) +
+                            " is not available with pls.solver_type aar (AAR starts from its own x0)");
         H.aar.configure(o, n, atol, rtol, maxiter);
     } else {
         const int64_t restart = (H.solver_type == "gmres") ? maxiter : 30;
@@ -512,6 +518,8 @@ int pls_solve(pls_handle *hh, const double *b, double *x, pls_result *res) {
         do_setup(H);
         DBuf<double> bi(H.n), xi(H.n);
         to_internal(H, b, bi.p);
+        ensure_ready(H);
+        if (H.outer && H.outer->guess_nonzero && !H.outer->guess_fischer) to_internal(H, x, xi.p);  // x is read only then
         solve_device(H, bi.p, xi.p);
         from_internal(H, xi.p, x);
         if (res) *res = H.res;
@@ -617,6 +625,31 @@ int pls_get_gmres_orthog_stats(pls_handle *hh, const char *prefix, int64_t *stat
         stats[0] = found->stat_orth_steps;
         stats[1] = found->stat_orth_second;
         stats[2] = found->orthog;
+    })
+}
+int pls_get_ksp_guess_stats(pls_handle *hh, const char *prefix, int64_t stats[6], double *last_reduction) {
+    PLS_TRY({
+        const KSP *found = find_ksp(*reinterpret_cast<Handle *>(hh), prefix, stats, "pls_get_ksp_guess_stats");
+        stats[0] = found->guess_fischer ? 1 : 0;
+        stats[1] = found->guess_fischer ? found->guess_m : 0;
+        stats[2] = found->guess_fischer ? found->guess_size : 0;
+        stats[3] = found->stat_guess_formed;
+        stats[4] = found->stat_guess_skipped;
+        stats[5] = found->stat_guess_resets;
+        if (last_reduction) *last_reduction = found->guess_last_reduction;
+    })
+}
+int pls_get_ksp_guess_info(pls_handle *hh, const char *prefix, int64_t *reads_x, double *seconds) {
+    PLS_TRY({
+        Handle &H = *reinterpret_cast<Handle *>(hh);
+        if (!prefix || !reads_x || !seconds) throw Error("pls_get_ksp_guess_info: null argument");
+        ensure_ready(H);  // (the options are read when the solver is created)
+        *reads_x = 0;
+        *seconds = std::nan("");
+        if (std::string(prefix) == "global_" && !H.outer) return 0;  // AAR: no outer KSP, x is output only
+        const KSP *found = find_ksp(H, prefix, seconds, "pls_get_ksp_guess_info");
+        *reads_x = found->guess_nonzero && !found->guess_fischer ? 1 : 0;
+        if (found->guess_timing) *seconds = found->guess_seconds;
     })
 }
 int pls_get_gmres_basis_stats(pls_handle *hh, const char *prefix, int64_t *stats) {
@@ -847,6 +880,7 @@ int pls_update_matrices(pls_handle *hh, const pls_csr *A, const pls_csr *P, cons
             H.A.sell.reset();
             H.A.tag = 1;
             if (H.solver_ready) build_sell(H.A, H.ctx);
+            if (H.outer) H.outer->guess_reset();  // B = A X no longer holds (PETSc's operator-state check)
         }
         if (P) upload_permuted(P, H, inv, H.P);
         if (Pdiff) {

@@ -1280,6 +1280,166 @@ void launch_lincomb(int64_t n, int k, const double *V, int64_t ldv, const double
     if (n > 0) k_lincomb<<<stream_grid(n), TPB, 0, st>>>(n, k, V, ldv, c_dev, y);
 }
 
+// ------------------------------------------- Fischer guess (KSPGuess, model 2) --
+// The update of the projection space after a solve (KSP::guess_update): with y = A x and
+// alpha = B^T y, xo = x - sum_j alpha_j X_j and yo = y - sum_j alpha_j B_j (j ascending, as
+// VecMAXPY), written straight into slot m of X and B (xo, yo: column m, never a column
+// read), and one partial ||yo||^2 per block for k_final.  k_maxpy_norm's data path: chunks
+// on even rows, 16-B loads of row pairs, two pairs per trip, GU_NJ column pairs (X_j, B_j)
+// loaded ahead of their FMAs (16 loads in flight per lane), the odd tail row in thread 0.
+// m = 0 is a copy plus a norm.  x and y are 16-B aligned (the host checks x).  The second
+// Gram-Schmidt pass runs in place, x = xo and y = yo (every row is read and written by one
+// thread), so those four pointers carry no restrict.
+static constexpr int GU_NJ = 4;
+__global__ __launch_bounds__(TPB) void k_guess_update(int64_t n, int m, const double *__restrict__ X,
+                                                      const double *__restrict__ B, int64_t ldv,
+                                                      const double *__restrict__ alpha,
+                                                      const double *x, const double *y, double *xo, double *yo,
+                                                      double *partial) {
+    __shared__ double lds[TPB / 64];
+    __shared__ double as[GUESS_MAX];
+    for (int j = threadIdx.x; j < m && j < GUESS_MAX; j += TPB) as[j] = alpha[j];
+    __syncthreads();
+    int64_t s, e;
+    chunk_even(n, gridDim.x, blockIdx.x, s, e);
+    double a = 0.0;
+    int64_t i = s + 2 * threadIdx.x;
+    for (; i + 2 * TPB + 1 < e; i += 4 * TPB) {
+        cgs_d2 xa = *reinterpret_cast<const cgs_d2 *>(x + i);
+        cgs_d2 xb = *reinterpret_cast<const cgs_d2 *>(x + i + 2 * TPB);
+        cgs_d2 ya = *reinterpret_cast<const cgs_d2 *>(y + i);
+        cgs_d2 yb = *reinterpret_cast<const cgs_d2 *>(y + i + 2 * TPB);
+        int j = 0;
+        for (; j + GU_NJ <= m; j += GU_NJ) {
+            cgs_d2 pa[GU_NJ], pb[GU_NJ], qa[GU_NJ], qb[GU_NJ];
+#pragma unroll
+            for (int u = 0; u < GU_NJ; ++u) {
+                pa[u] = *reinterpret_cast<const cgs_d2 *>(X + (int64_t)(j + u) * ldv + i);
+                pb[u] = *reinterpret_cast<const cgs_d2 *>(X + (int64_t)(j + u) * ldv + i + 2 * TPB);
+                qa[u] = *reinterpret_cast<const cgs_d2 *>(B + (int64_t)(j + u) * ldv + i);
+                qb[u] = *reinterpret_cast<const cgs_d2 *>(B + (int64_t)(j + u) * ldv + i + 2 * TPB);
+            }
+#pragma unroll
+            for (int u = 0; u < GU_NJ; ++u) {
+                const double aj = as[j + u];
+                xa.x -= aj * pa[u].x;
+                xa.y -= aj * pa[u].y;
+                xb.x -= aj * pb[u].x;
+                xb.y -= aj * pb[u].y;
+                ya.x -= aj * qa[u].x;
+                ya.y -= aj * qa[u].y;
+                yb.x -= aj * qb[u].x;
+                yb.y -= aj * qb[u].y;
+            }
+        }
+        for (; j < m; ++j) {
+            const cgs_d2 pa = *reinterpret_cast<const cgs_d2 *>(X + (int64_t)j * ldv + i);
+            const cgs_d2 pb = *reinterpret_cast<const cgs_d2 *>(X + (int64_t)j * ldv + i + 2 * TPB);
+            const cgs_d2 qa = *reinterpret_cast<const cgs_d2 *>(B + (int64_t)j * ldv + i);
+            const cgs_d2 qb = *reinterpret_cast<const cgs_d2 *>(B + (int64_t)j * ldv + i + 2 * TPB);
+            const double aj = as[j];
+            xa.x -= aj * pa.x;
+            xa.y -= aj * pa.y;
+            xb.x -= aj * pb.x;
+            xb.y -= aj * pb.y;
+            ya.x -= aj * qa.x;
+            ya.y -= aj * qa.y;
+            yb.x -= aj * qb.x;
+            yb.y -= aj * qb.y;
+        }
+        *reinterpret_cast<cgs_d2 *>(xo + i) = xa;
+        *reinterpret_cast<cgs_d2 *>(xo + i + 2 * TPB) = xb;
+        *reinterpret_cast<cgs_d2 *>(yo + i) = ya;
+        *reinterpret_cast<cgs_d2 *>(yo + i + 2 * TPB) = yb;
+        a += ya.x * ya.x;
+        a += ya.y * ya.y;
+        a += yb.x * yb.x;
+        a += yb.y * yb.y;
+    }
+    for (; i + 1 < e; i += 2 * TPB) {
+        cgs_d2 xt = *reinterpret_cast<const cgs_d2 *>(x + i);
+        cgs_d2 yt = *reinterpret_cast<const cgs_d2 *>(y + i);
+        int j = 0;
+        for (; j + GU_NJ <= m; j += GU_NJ) {
+            cgs_d2 p[GU_NJ], q[GU_NJ];
+#pragma unroll
+            for (int u = 0; u < GU_NJ; ++u) {
+                p[u] = *reinterpret_cast<const cgs_d2 *>(X + (int64_t)(j + u) * ldv + i);
+                q[u] = *reinterpret_cast<const cgs_d2 *>(B + (int64_t)(j + u) * ldv + i);
+            }
+#pragma unroll
+            for (int u = 0; u < GU_NJ; ++u) {
+                const double aj = as[j + u];
+                xt.x -= aj * p[u].x;
+                xt.y -= aj * p[u].y;
+                yt.x -= aj * q[u].x;
+                yt.y -= aj * q[u].y;
+            }
+        }
+        for (; j < m; ++j) {
+            const cgs_d2 p = *reinterpret_cast<const cgs_d2 *>(X + (int64_t)j * ldv + i);
+            const cgs_d2 q = *reinterpret_cast<const cgs_d2 *>(B + (int64_t)j * ldv + i);
+            const double aj = as[j];
+            xt.x -= aj * p.x;
+            xt.y -= aj * p.y;
+            yt.x -= aj * q.x;
+            yt.y -= aj * q.y;
+        }
+        *reinterpret_cast<cgs_d2 *>(xo + i) = xt;
+        *reinterpret_cast<cgs_d2 *>(yo + i) = yt;
+        a += yt.x * yt.x;
+        a += yt.y * yt.y;
+    }
+    if (((e - s) & 1) && threadIdx.x == 0) {
+        const int64_t l = e - 1;
+        double xt = x[l], yt = y[l];
+        for (int j = 0; j < m; ++j) {
+            xt -= as[j] * X[(int64_t)j * ldv + l];
+            yt -= as[j] * B[(int64_t)j * ldv + l];
+        }
+        xo[l] = xt;
+        yo[l] = yt;
+        a += yt * yt;
+    }
+    a = block_sum(a, lds);
+    if (threadIdx.x == 0) partial[blockIdx.x] = a;
+}
+void launch_guess_update(int64_t n, int m, double *X, double *B, int64_t ldv, const double *alpha_dev,
+                         const double *x, const double *y, double *partial, double *out, hipStream_t st) {
+    // (x == nullptr: in place, the column pair already in slot m)
+    if (m < 0 || m >= GUESS_MAX) return;  // (never: the host keeps m < size <= GUESS_MAX)
+    const int nb = reduce_blocks(n);
+    if (!x) {
+        x = X + (int64_t)m * ldv;
+        y = B + (int64_t)m * ldv;
+    }
+    k_guess_update<<<nb, TPB, 0, st>>>(n, m, X, B, ldv, alpha_dev, x, y, X + (int64_t)m * ldv,
+                                       B + (int64_t)m * ldv, partial);
+    k_final<<<1, TPB, 0, st>>>(nb, partial, out, 0);  // ||yo||^2 (rank-local)
+}
+
+// the two new columns scaled by a = 1 / ||yo|| in one launch (u, v: 16-B aligned)
+__global__ __launch_bounds__(TPB) void k_scale2(int64_t n, double a, double *__restrict__ u, double *__restrict__ v) {
+    const int64_t np = n >> 1;
+    for (int64_t p = (int64_t)blockIdx.x * TPB + threadIdx.x; p < np; p += (int64_t)gridDim.x * TPB) {
+        cgs_d2 s = *reinterpret_cast<const cgs_d2 *>(u + 2 * p);
+        cgs_d2 t = *reinterpret_cast<const cgs_d2 *>(v + 2 * p);
+        s.x *= a;
+        s.y *= a;
+        t.x *= a;
+        t.y *= a;
+        *reinterpret_cast<cgs_d2 *>(u + 2 * p) = s;
+        *reinterpret_cast<cgs_d2 *>(v + 2 * p) = t;
+    }
+    if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
+        u[n - 1] *= a;
+        v[n - 1] *= a;
+    }
+}
+void launch_scale2(int64_t n, double a, double *u, double *v, hipStream_t st) {
+    if (n > 0) k_scale2<<<stream_grid((n + 1) / 2), TPB, 0, st>>>(n, a, u, v);
+}
+
 // ------------------------------------------ compressed-basis GMRES (fp32 V) --
 // The counterparts of k_mdot / k_maxpy_norm / k_mgs_step / k_lincomb for a
 // Krylov basis stored in fp32 (pls_gmres_basis single): the columns are read as

@@ -151,6 +151,16 @@ void launch_mgs_step(int64_t n, const double *vprev, const double *hprev, const 
 // y = sum_j c[j] * V[:, j] (c on device)
 void launch_lincomb(int64_t n, int k, const double *V, int64_t ldv, const double *c_dev, double *y,
                     hipStream_t st);
+// Fischer guess, model 2 (ksp_guess_type fischer): the space's update after a solve.  X, B: the
+// stored columns (stride ldv, a multiple of 64 doubles; columns 512-B aligned), m < GUESS_MAX of
+// them; x, y = A x (16-B aligned); alpha = B^T y on the device.  Writes x - X alpha and
+// y - B alpha into column m of X and B and ||y - B alpha||^2 (rank-local) into *out.  x == nullptr:
+// in place on the pair already in column m (the second Gram-Schmidt pass).
+static constexpr int GUESS_MAX = 64;
+void launch_guess_update(int64_t n, int m, double *X, double *B, int64_t ldv, const double *alpha_dev,
+                         const double *x, const double *y, double *partial, double *out, hipStream_t st);
+// u *= a, v *= a (both 16-B aligned)
+void launch_scale2(int64_t n, double a, double *u, double *v, hipStream_t st);
 // Compressed-basis GMRES (pls_gmres_basis single): the same four over a basis stored in fp32
 // (ldv a multiple of 128 floats), w and all sums fp64 ...
 void launch_mdot_f32(int64_t n, int k, const float *V, int64_t ldv, const double *w, double *partial, double *out,

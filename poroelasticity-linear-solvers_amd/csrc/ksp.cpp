@@ -159,7 +159,7 @@ void KSP::ensure_work(Ctx &c) {
 int KSP::converged(int it, double r) {
     auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     if (it == 0) {
-        rnorm0 = r;
+        rnorm0 = guess_rnorm0 > 0.0 ? guess_rnorm0 : r;  // (a guessed solve: ||b|| or ||B b||, solve_guessed)
         ttol = std::max(rtol * rnorm0, atol);
         if (time_limit > 0) t_start = now();
     }
@@ -184,6 +184,19 @@ int KSP::record(int it, double r, bool test) {
 
 void KSP::solve(const double *b, double *x, Ctx &c) {
     history.clear();
+    if (guess_nonzero || guess_fischer) solve_guessed(b, x, c);
+    else run(b, x, c);
+    stat_its += its;
+    stat_max = std::max<int64_t>(stat_max, its);
+    ++stat_solves;
+    stat_div += reason < 0 ? 1 : 0;
+    if (reason < 0) stat_last_neg = reason;
+    c.check_bounds();
+    if (vf_canary) check_basis_bounds(c);
+    if (guess_canary) check_guess_bounds(c);
+}
+
+void KSP::run(const double *b, double *x, Ctx &c) {
     if (type == "preonly") {
         pc->apply(b, x, c);
         its = 1;
@@ -197,13 +210,205 @@ void KSP::solve(const double *b, double *x, Ctx &c) {
         else if (type == "cg") device_loop_allowed() ? solve_cg_dev(b, x, c) : solve_cg(b, x, c);
         else device_loop_allowed() ? solve_bcgs_dev(b, x, c) : solve_bcgs(b, x, c);  // bcgs: no other type is left
     }
-    stat_its += its;
-    stat_max = std::max<int64_t>(stat_max, its);
-    ++stat_solves;
-    stat_div += reason < 0 ? 1 : 0;
-    if (reason < 0) stat_last_neg = reason;
-    c.check_bounds();
-    if (vf_canary) check_basis_bounds(c);
+}
+
+// ------------------------------------------------------- the initial guess --
+// KSPSolve with a guess: x0 = FormGuess(b) when a guess object exists, else the
+// incoming x; r0 = b - A x0; the type's own zero-guess solve of A d = r0 (run: no solver loop knows of
+// the guess, and restarts evaluate r0 - A d, which is b - A x to rounding); x = x0 + d; the space's update.
+// KSPConvergedDefault with a nonzero guess measures rtol and dtol against ||b|| (right preconditioning,
+// norm unpreconditioned) or ||B b|| (the preconditioned norm: one more PC application) instead of the first
+// residual; where that norm is 0 the first residual stays.  The norms of b and r0 come back in one read-back.
+namespace {
+bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
+constexpr double GUESS_REFORM = 1e-2;  // ||y'|| / ||y|| below which B's new column is formed again as A x'
+}  // namespace
+
+void KSP::ensure_guess(Ctx &c) {
+    c.ensure_partial(n, guess_size + 2);
+    const int64_t nn = std::max<int64_t>(n, 1);
+    if (!gx0.p) {
+        for (DBuf<double> *v : {&gx0, &gr0, &gy}) v->alloc(nn);
+        gd.alloc(2 * GUESS_MAX + 16);  // alpha, two norms, the second pass's beta; three norms of a solve's start
+    }
+    if (guess_timing && !guess_ev[0])
+        for (hipEvent_t &e : guess_ev) HIPCHK(hipEventCreate(&e));
+    if (guess_fischer && !gX.p) {
+        guess_ldv = (nn + 63) & ~(int64_t)63;  // 512-B aligned columns, the Krylov basis's stride
+        guess_canary = c.debug_bounds;
+        const size_t count = (size_t)guess_size * guess_ldv, guard = guess_canary ? Ctx::CANARY : 0;
+        try {
+            gX.alloc(count + guard);
+            gB.alloc(count + guard);
+        } catch (const Error &e) {
+            gX.release();
+            gB.release();
+            (void)hipGetLastError();
+            throw Error("ksp_guess_type fischer (" + prefix + "): the projection space of 2 x " +
+                        std::to_string(guess_size) + " columns (" + std::to_string(2 * count * sizeof(double)) +
+                        " bytes) could not be allocated: " + e.what());
+        }
+        if (guess_canary)
+            for (DBuf<double> *v : {&gX, &gB})
+                HIPCHK(hipMemsetAsync(v->p + count, 0xA5, sizeof(double) * Ctx::CANARY, c.st));
+        guess_m = 0;
+    }
+}
+
+// pls.debug_bounds: the guard doubles behind the two column stores, as check_basis_bounds checks the fp32 basis's
+void KSP::check_guess_bounds(Ctx &c) {
+    if (!gX.p) return;
+    std::vector<unsigned char> g(sizeof(double) * Ctx::CANARY);
+    for (DBuf<double> *v : {&gX, &gB}) {
+        HIPCHK(hipMemcpyAsync(g.data(), v->p + (v->n - Ctx::CANARY), g.size(), hipMemcpyDeviceToHost, c.st));
+        c.sync();
+        for (size_t i = 0; i < g.size(); ++i)
+            if (g[i] != 0xA5)
+                throw Error("pls.debug_bounds: the canary behind the Fischer guess's columns (" + prefix +
+                            ") was overwritten at byte +" + std::to_string(i));
+    }
+}
+
+void KSP::guess_reset() {
+    if (!guess_fischer) return;
+    guess_m = 0;
+    ++stat_guess_resets;
+}
+
+// FormGuess(b): alpha = B^T b (k_mdot, the global sum in rank order), x0 = sum_i alpha_i X_i with i
+// ascending (k_lincomb).  Nothing is read back.
+void KSP::guess_form(const double *b, double *x0, Ctx &c) {
+    const int m = (int)guess_m;
+    if (m == 0) {
+        launch_set(n, 0.0, x0, c.st);
+        return;
+    }
+    if (!aligned16(b)) {  // (a block's rows inside a longer vector: k_mdot loads 16 bytes)
+        launch_copy(n, b, gy.p, c.st);
+        b = gy.p;
+    }
+    launch_mdot(n, m, nullptr, gB.p, guess_ldv, b, c.partials(n, m), gd.p, c.st);
+    c.comm->global_sum_dev(gd.p, m, c.st);
+    launch_lincomb(n, m, gX.p, guess_ldv, gd.p, x0, c.st);
+}
+
+// Update(b, x) of Fischer's model 2: y = A x, alpha = B^T y, x' = x - X alpha, y' = y - B alpha, and the
+// pair (x', y') / ||y'|| appended when ||y'|| > tol ||y||.  A full space is emptied first.  The projection
+// runs twice (beta = B^T y', x' -= X beta, y' -= B beta, in place in the new slot): one pass leaves B^T y' at
+// eps ||y|| / ||y'||, and consecutive solutions of a time loop differ by 1e-3 .. 1e-6, so the columns lost
+// their orthogonality within one fill of the space.  A solve that made no iteration returned the guess
+// itself, a combination of the stored columns, for which ||y'|| is 0 in exact arithmetic and rounding
+// noise when computed (1e-13 ||y||, above the default tol): it is counted as skipped without computing it,
+// unless the space is full and about to be emptied.  Where ||y'|| < GUESS_REFORM ||y|| the new column of B is
+// formed again as a product, so that B = A X holds to rounding for nearly dependent solutions too (a third
+// product with A, for those updates only).  One read-back of the m + 2 scalars (one more when the space is
+// emptied -- ||y|| first, which tells whether x is finite -- and when the column is formed again).
+void KSP::guess_update(const double *x, Ctx &c) {
+    if (its == 0 && guess_m > 0 && guess_m < guess_size) {
+        ++stat_guess_skipped;
+        return;
+    }
+    if (!aligned16(x)) {
+        launch_copy(n, x, gx0.p, c.st);
+        x = gx0.p;
+    }
+    double *y = gy.p, *d = gd.p;
+    A->apply(x, y, c);
+    auto read_back = [&](int count) {
+        double *hs = c.host_scalars(count);
+        HIPCHK(hipMemcpyAsync(hs, d, sizeof(double) * count, hipMemcpyDeviceToHost, c.st));
+        c.sync();
+        return hs;
+    };
+    if (guess_m == guess_size) {
+        launch_dot(n, y, y, c.partials(n, 1), d, c.st);
+        c.comm->global_sum_dev(d, 1, c.st);
+        if (!std::isfinite(read_back(1)[0])) return;  // x holds NaN or Inf: the space stays
+        guess_m = 0;
+        ++stat_guess_resets;
+    }
+    const int m = (int)guess_m;
+    double *yo = gB.p + (int64_t)m * guess_ldv, *beta = d + m + 2;
+    launch_mdot(n, m, nullptr, gB.p, guess_ldv, y, c.partials(n, m), d, c.st);
+    launch_dot(n, y, y, c.partials(n, 1), d + m, c.st);
+    c.comm->global_sum_dev(d, m + 1, c.st);
+    launch_guess_update(n, m, gX.p, gB.p, guess_ldv, d, x, y, c.partials(n, 1), d + m + 1, c.st);
+    if (m > 0) {
+        launch_mdot(n, m, nullptr, gB.p, guess_ldv, yo, c.partials(n, m), beta, c.st);
+        c.comm->global_sum_dev(beta, m, c.st);
+        launch_guess_update(n, m, gX.p, gB.p, guess_ldv, beta, nullptr, nullptr, c.partials(n, 1), d + m + 1, c.st);
+    }
+    c.comm->global_sum_dev(d + m + 1, 1, c.st);
+    const double *hs = read_back(m + 2);
+    if (!std::isfinite(hs[m]) || !std::isfinite(hs[m + 1])) return;
+    const double nu0 = std::sqrt(hs[m]), nu = std::sqrt(hs[m + 1]);
+    if (nu > guess_tol * nu0 && nu > 0.0) {
+        double *xo = gX.p + (int64_t)m * guess_ldv;
+        launch_scale2(n, 1.0 / nu, xo, yo, c.st);
+        if (nu < GUESS_REFORM * nu0) {
+            // y' carries the rounding of y = A x, eps nu0, which is eps nu0 / nu of the normalised column
+            // (7e-11 at nu = 1e-6 nu0): B's column is formed again as the product A x', projected once more
+            // (the new column is orthogonal to the others to eps nu0 / nu only) and normalised again
+            A->apply(xo, yo, c);
+            launch_mdot(n, m, nullptr, gB.p, guess_ldv, yo, c.partials(n, m), beta, c.st);
+            c.comm->global_sum_dev(beta, m, c.st);
+            launch_guess_update(n, m, gX.p, gB.p, guess_ldv, beta, nullptr, nullptr, c.partials(n, 1), d + m + 1,
+                                c.st);
+            c.comm->global_sum_dev(d + m + 1, 1, c.st);
+            const double nu2 = std::sqrt(read_back(m + 2)[m + 1]);
+            if (!(nu2 > 0.0) || !std::isfinite(nu2)) return;  // (the slot is not counted: nothing was appended)
+            launch_scale2(n, 1.0 / nu2, xo, yo, c.st);
+        }
+        ++guess_m;
+    } else {
+        ++stat_guess_skipped;
+    }
+}
+
+void KSP::solve_guessed(const double *b, double *x, Ctx &c) {
+    ensure_work(c);
+    ensure_guess(c);
+    double *x0 = gx0.p, *r0 = gr0.p, *d = gd.p + 2 * GUESS_MAX + 4;
+    if (guess_timing) HIPCHK(hipEventRecord(guess_ev[0], c.st));
+    if (guess_fischer) {
+        guess_form(b, x0, c);
+        ++stat_guess_formed;
+    } else {
+        launch_copy(n, x, x0, c.st);
+    }
+    A->residual(x0, b, r0, c);
+    const bool pnorm = norm == "preconditioned";
+    launch_dot(n, b, b, c.partials(n, 1), d, c.st);
+    launch_dot(n, r0, r0, c.partials(n, 1), d + 1, c.st);
+    if (pnorm) {
+        pc->apply(b, gy.p, c);
+        launch_dot(n, gy.p, gy.p, c.partials(n, 1), d + 2, c.st);
+    }
+    c.comm->global_sum_dev(d, pnorm ? 3 : 2, c.st);
+    if (guess_timing) HIPCHK(hipEventRecord(guess_ev[1], c.st));
+    double *hs = c.host_scalars(3);
+    HIPCHK(hipMemcpyAsync(hs, d, sizeof(double) * (pnorm ? 3 : 2), hipMemcpyDeviceToHost, c.st));
+    c.sync();
+    const double bn = std::sqrt(hs[0]), rn = std::sqrt(hs[1]);
+    guess_last_reduction = rn / bn;
+    guess_rnorm0 = norm == "none" ? 0.0 : pnorm ? std::sqrt(hs[2]) : bn;
+    if (!(guess_rnorm0 > 0.0)) guess_rnorm0 = 0.0;  // (0, or NaN: the first residual's norm stays)
+    struct Restore {
+        double &v;
+        ~Restore() { v = 0.0; }
+    } restore{guess_rnorm0};
+    run(r0, x, c);
+    if (guess_timing) HIPCHK(hipEventRecord(guess_ev[2], c.st));
+    launch_axpby(n, 1.0, x0, 1.0, x, c.st);  // x = x0 + d
+    if (guess_fischer) guess_update(x, c);
+    if (guess_timing) {  // everything the guess adds to the zero-guess solve: before it and after it
+        float a = 0.f, u = 0.f;
+        HIPCHK(hipEventRecord(guess_ev[3], c.st));
+        HIPCHK(hipEventSynchronize(guess_ev[3]));
+        HIPCHK(hipEventElapsedTime(&a, guess_ev[0], guess_ev[1]));
+        HIPCHK(hipEventElapsedTime(&u, guess_ev[2], guess_ev[3]));
+        guess_seconds = ((double)a + (double)u) * 1e-3;
+    }
 }
 
 // pls.debug_bounds: the guard bytes behind the fp32 basis, as Ctx::check_bounds checks those behind the partials
@@ -219,6 +424,8 @@ void KSP::check_basis_bounds(Ctx &c) {
 }
 
 KSP::~KSP() {
+    for (hipEvent_t e : guess_ev)
+        if (e) (void)hipEventDestroy(e);
     if (stats && stat_solves)
         fprintf(stderr, "[ksp %s%s] %lld solves, %lld its (mean %.1f, max %lld)\n", prefix.c_str(), type.c_str(),
                 (long long)stat_solves, (long long)stat_its, (double)stat_its / (double)stat_solves, (long long)stat_max);
@@ -1185,6 +1392,45 @@ std::unique_ptr<KSP> make_ksp(const std::string &prefix, const Options &o, const
                         "ksp_gmres_modifiedgramschmidt): the fp32 step kernel has no single-launch sums");
     }
     k->resolve_side_norm(o.str(prefix + "ksp_pc_side", ""), o.str(prefix + "ksp_norm_type", ""));
+    {
+        // the initial guess: ksp_initial_guess_nonzero (the outer KSP only) and KSPGuess
+        const std::string nzkey = prefix + "ksp_initial_guess_nonzero", gkey = prefix + "ksp_guess_type";
+        const std::string mkey = prefix + "ksp_guess_fischer_model", tkey = prefix + "ksp_guess_fischer_tol";
+        if (o.flag(nzkey, false)) {
+            if (prefix != "global_")
+                throw Error(nzkey + ": a nonzero initial guess is available for the outer solver (global_) only, " +
+                            "not for prefix '" + prefix + "': the block preconditioner's inner x vectors are scratch");
+            if (k->type == "preonly")
+                throw Error(nzkey + ": KSPPREONLY cannot start from a nonzero initial guess");
+            k->guess_nonzero = true;
+        }
+        const std::string gt = o.str(gkey, "none");
+        if (gt != "none" && gt != "fischer")
+            throw Error(gkey + ": unknown value '" + gt + "' (available: none, fischer)");
+        if (gt == "fischer") {
+            if (k->type == "preonly")
+                throw Error(gkey + " fischer is not available with ksp_type preonly (" + prefix + ")");
+            k->guess_fischer = true;
+            int64_t model = 2, size = 10;
+            if (o.has(mkey)) {
+                const std::vector<double> v = comma_list(o.str(mkey, ""), mkey);
+                if (v.size() != 2 || v[0] != std::floor(v[0]) || v[1] != std::floor(v[1]))
+                    throw Error(mkey + " takes <model>,<size> (one token of two integers)");
+                model = (int64_t)v[0];
+                size = (int64_t)v[1];
+            }
+            if (model != 2)
+                throw Error(mkey + ": model " + std::to_string(model) + " is not available; only model 2 " +
+                            "(least squares, valid for a nonsymmetric operator) is built");
+            if (size < 1 || size > GUESS_MAX)
+                throw Error(mkey + ": size " + std::to_string(size) + " is outside 1 <= size <= " +
+                            std::to_string(GUESS_MAX));
+            k->guess_size = size;
+            k->guess_tol = o.num(tkey, 32.0 * 2.220446049250313e-16);
+        }
+        k->guess_timing = o.flag("pls.ksp_guess_timing", false);
+        k->guess_last_reduction = std::nan("");
+    }
     k->poly_fuse_jacobi = o.flag("pls.poly_fuse_jacobi", true);
     if (k->type == "richardson") {
         if (o.has(prefix + "ksp_richardson_self_scale"))

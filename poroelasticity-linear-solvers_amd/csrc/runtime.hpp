@@ -9,6 +9,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdint>
 #include <map>
 #include <functional>
@@ -515,6 +516,25 @@ struct KSP {
     DBuf<int64_t> cgI;
     bool cg_device = true;     // pls.cg_device: CG's recurrences on the device (no read-back per iteration)
     int64_t allocated_k = -1;
+    // The initial guess.  ksp_initial_guess_nonzero (the outer KSP only): x0 is the
+    // incoming x.  ksp_guess_type fischer (KSPGuess, model 2): x0 = X B^T b over up to guess_size stored
+    // column pairs with B = A X orthonormal, the space updated after every solve.  Either way the solve runs
+    // in correction form -- a zero-guess solve of A d = b - A x0 by the type's own loop, x = x0 + d -- with
+    // KSPConvergedDefault's rnorm0 taken from b (guess_rnorm0) instead of the first residual.
+    bool guess_nonzero = false, guess_fischer = false;
+    int64_t guess_size = 10;           // ksp_guess_fischer_model 2,<size>
+    double guess_tol = 0.0;            // ksp_guess_fischer_tol
+    int64_t guess_m = 0, guess_ldv = 0;  // columns stored now; their stride (a multiple of 64 doubles)
+    DBuf<double> gX, gB;               // the space, allocated at the first solve (2 x guess_size x guess_ldv)
+    DBuf<double> gx0, gr0, gy, gd;     // x0, r0 = b - A x0, y = A x (and scratch), the projections' scalars
+    bool guess_canary = false;         // pls.debug_bounds: Ctx::CANARY guard doubles behind gX and gB
+    int64_t stat_guess_formed = 0, stat_guess_skipped = 0, stat_guess_resets = 0;
+    double guess_last_reduction = NAN;  // ||b - A x0|| / ||b|| of the most recent solve (NaN before the first)
+    double guess_rnorm0 = 0.0;          // > 0 while a guessed solve runs: rnorm0 of the convergence test
+    bool guess_timing = false;          // pls.ksp_guess_timing: HIP-event time of what the guess adds to a solve
+                                        // (forming x0, r0 and its norms; x = x0 + d and the space's update)
+    double guess_seconds = 0.0;         // ... of the most recent solve
+    void guess_reset();                 // empties the space and counts a reset (the operator changed)
     void set_type_defaults();
     void resolve_side_norm(const std::string &side, const std::string &nt);
     void solve(const double *b, double *x, Ctx &c);
@@ -529,6 +549,14 @@ struct KSP {
     }
   private:
     void ensure_work(Ctx &c);
+    void run(const double *b, double *x, Ctx &c);  // the type's own solve, from a zero guess
+    // the wrapper around run() when a guess is in use, and the Fischer space's two operations
+    void solve_guessed(const double *b, double *x, Ctx &c);
+    void ensure_guess(Ctx &c);
+    void guess_form(const double *b, double *x0, Ctx &c);
+    void guess_update(const double *x, Ctx &c);
+    void check_guess_bounds(Ctx &c);
+    hipEvent_t guess_ev[4] = {nullptr, nullptr, nullptr, nullptr};
     void solve_gmres(const double *b, double *x, Ctx &c);  // gmres and fgmres
     // one Arnoldi step: w orthogonalised against the first k columns of V; the Hessenberg
     // column's k entries into h (host), ||w||^2 returned

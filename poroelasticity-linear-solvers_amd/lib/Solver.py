@@ -59,8 +59,10 @@ class Solver:
 
     def solve(self, b, x):
         t0 = time()
-        xs, r = self.solver.solve(vec_array(b))
         xa = vec_array(x)
+        # x's contents are the initial guess iff -global_ksp_initial_guess_nonzero is set (the reference
+        # keeps setInitialGuessNonzero commented out, lib/Solver.py:94: with its option files x is output only)
+        xs, r = self.solver.solve(vec_array(b), xa if self.solver.initial_guess_nonzero() else None)
         xa[...] = xs
         self.its, self.reason = r.its, r.reason
         self.history = self.solver.history()

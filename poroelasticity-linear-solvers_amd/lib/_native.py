@@ -49,7 +49,7 @@ EXPORTS = [
     "pls_anderson_next", "pls_anderson_destroy", "pls_boomeramg_host_level", "pls_sparse_lu_analyze",
     "pls_get_ksp_stats", "pls_get_gmres_orthog_stats", "pls_get_chebyshev_bounds",
     "pls_hessenberg_eigenvalues", "pls_get_reuse_stats", "pls_get_ilu_fill",
-    "pls_get_gmres_basis_stats",
+    "pls_get_gmres_basis_stats", "pls_get_ksp_guess_stats", "pls_get_ksp_guess_info",
 ]
 
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p)
@@ -92,6 +92,8 @@ def lib():
     L.pls_get_ksp_stats.argtypes = [vp, C.c_char_p, vp]
     L.pls_get_gmres_orthog_stats.argtypes = [vp, C.c_char_p, vp]
     L.pls_get_gmres_basis_stats.argtypes = [vp, C.c_char_p, vp]
+    L.pls_get_ksp_guess_stats.argtypes = [vp, C.c_char_p, vp, C.POINTER(C.c_double)]
+    L.pls_get_ksp_guess_info.argtypes = [vp, C.c_char_p, C.POINTER(i64), C.POINTER(C.c_double)]
     L.pls_get_chebyshev_bounds.argtypes = [vp, C.c_char_p, vp]
     L.pls_get_ilu_fill.argtypes = [vp, C.c_char_p, vp]
     L.pls_get_reuse_stats.argtypes = [vp, vp]

@@ -163,9 +163,30 @@ class Handle:
         N.check(N.lib().pls_matmult(self.ptr, N.ptr(x), N.ptr(y)))
         return y
 
-    def solve(self, b):
+    def _guess_info(self, prefix):
+        rx, t = C.c_int64(), C.c_double()
+        N.check(N.lib().pls_get_ksp_guess_info(self.ptr, prefix.encode(), C.byref(rx), C.byref(t)))
+        return bool(rx.value), t.value
+
+    def initial_guess_nonzero(self):
+        """Does the outer solve read x as its initial guess?  libpls's own answer
+        (pls_get_ksp_guess_info; creates the solver if it was not yet)."""
+        return self._guess_info("global_")[0]
+
+    def solve(self, b, x0=None):
+        """x, result = KSPSolve(b).  ``x0``: the initial guess, read by libpls exactly when
+        -global_ksp_initial_guess_nonzero is set and no Fischer guess replaces it; passing one
+        otherwise is an error, and without one the guess is zero."""
         b = np.ascontiguousarray(b, dtype=np.float64)
-        x = np.empty_like(b)
+        if x0 is not None:
+            if not self.initial_guess_nonzero():
+                raise ValueError("Handle.solve: x0 given, but global_ksp_initial_guess_nonzero is not set "
+                                 "(or a Fischer guess replaces it): libpls would not read it")
+            x = np.array(x0, dtype=np.float64, order="C", copy=True)
+            if x.shape != b.shape:
+                raise ValueError("Handle.solve: x0 must have the shape of b")
+        else:
+            x = np.zeros_like(b)  # (read as the guess when the option is set, never otherwise)
         r = N.pls_result()
         N.check(N.lib().pls_solve(self.ptr, N.ptr(b), N.ptr(x), C.byref(r)))
         return x, r
@@ -241,6 +262,21 @@ class Handle:
         s = np.zeros(5, dtype=np.int64)
         N.check(N.lib().pls_get_gmres_basis_stats(self.ptr, prefix.encode(), N.ptr(s)))
         return tuple(int(v) for v in s)
+
+    def ksp_guess_stats(self, prefix):
+        """((type: 0 none, 1 fischer; columns stored now; size; guesses formed; updates skipped;
+        resets), ||b - A x0|| / ||b|| of the most recent guessed solve -- NaN before the first) of
+        the KSP with this options prefix (pls_get_ksp_guess_stats)."""
+        s = np.zeros(6, dtype=np.int64)
+        red = C.c_double()
+        N.check(N.lib().pls_get_ksp_guess_stats(self.ptr, prefix.encode(), N.ptr(s), C.byref(red)))
+        return tuple(int(v) for v in s), red.value
+
+    def ksp_guess_time(self, prefix):
+        """Seconds (HIP events) the most recent solve of that KSP spent on its guess: x0, r0 and the
+        norms before the zero-guess solve, x = x0 + d and the space's update after it; NaN unless
+        pls.ksp_guess_timing 1 (pls_get_ksp_guess_info)."""
+        return self._guess_info(prefix)[1]
 
     def chebyshev_bounds(self, prefix):
         """(emin, emax as used, the estimate's smallest and largest real part -- NaN when the bounds
