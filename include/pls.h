@@ -200,12 +200,23 @@ int pls_get_sizes(pls_handle *h, int64_t *n, int64_t *ns, int64_t *nf, int64_t *
 int pls_pc_apply(pls_handle *h, const double *x, double *y);
 int pls_solve(pls_handle *h, const double *b, double *x, pls_result *res);
 int pls_matmult(pls_handle *h, const double *x, double *y);
+/* y = A^ x with the low-precision copy of the outer operator that
+ * -<prefix>pls_gmres_operator single multiplies with: A's SELL-64/D16 layout,
+ * every stored value rounded to nearest-even fp32 once (the fp32 stream is
+ * built on demand); x, y, every product and every sum are fp64.  An error
+ * when A's layout is int32 SELL-64 or CSR, has a SELL/B3 part, or holds a
+ * finite value that is infinite in fp32.                                     */
+int pls_matmult_single(pls_handle *h, const double *x, double *y);
 
 /* Device-vector entry points: d_b / d_x are device pointers in the handle's
  * internal field-major order (no host traffic, no permutation).             */
 int pls_solve_device(pls_handle *h, const double *d_b, double *d_x, pls_result *res);
 int pls_pc_apply_device(pls_handle *h, const double *d_x, double *d_y);
 int pls_matmult_device(pls_handle *h, const double *d_x, double *d_y);
+/* pls_matmult_single on device vectors (with pls.reuse_coupling_probe and an
+ * outer solver with pls_gmres_operator single: the low product as GMRES forms
+ * it after a preconditioner application).                                    */
+int pls_matmult_single_device(pls_handle *h, const double *d_x, double *d_y);
 /* Synthetic right-hand side (field-major) written to a device vector.        */
 int pls_synthetic_rhs_device(pls_handle *h, uint64_t seed, double *d_b);
 /* Device buffer helpers (so hosts without a GPU runtime binding can drive it) */
@@ -239,6 +250,15 @@ int pls_get_gmres_orthog_stats(pls_handle *h, const char *prefix, int64_t stats[
  * [4] confirmations that failed and led to another cycle ([2]-[4] stay 0 with
  * a double basis).  An unknown prefix or a KSP of another type is an error.  */
 int pls_get_gmres_basis_stats(pls_handle *h, const char *prefix, int64_t stats[5]);
+/* The operator inside the Arnoldi step of the gmres / fgmres KSP with this
+ * prefix (<prefix>pls_gmres_operator, with <prefix>pls_gmres_basis single
+ * only): stats[0] its precision (0 double, 1 single), [1] bytes of the fp32
+ * value streams its operator holds (the reduced layout of the coupling reuse
+ * included), and since setup [2] products with the low-precision operator,
+ * [3] fp64 products (cycle-start residuals, the guesses' products; with a
+ * double operator also the Arnoldi products of the fp32-basis cycle).  An
+ * unknown prefix or a KSP of another type is an error.                       */
+int pls_get_gmres_operator_stats(pls_handle *h, const char *prefix, int64_t stats[4]);
 /* The initial guess of the KSP with this prefix (-<prefix>ksp_guess_type
  * none|fischer, -<prefix>ksp_guess_fischer_model 2,<size>,
  * -<prefix>ksp_guess_fischer_tol; -global_ksp_initial_guess_nonzero for the
@@ -267,6 +287,10 @@ int pls_get_ksp_guess_info(pls_handle *h, const char *prefix, int64_t *reads_x, 
  * path is eligible for the next solve (decided when the solver is created and
  * again after pls_update_matrices), else 0.                                  */
 int pls_get_reuse_stats(pls_handle *h, int64_t stats[3]);
+/* The rows of the coupling reuse: mask[i] = 1 (n bytes, the caller's row
+ * order) where the reduced outer product starts row i from the block
+ * preconditioner's raw sum, all 0 while the reduced path is not eligible.    */
+int pls_get_reuse_rows(pls_handle *h, uint8_t *mask);
 /* The eigenvalue bounds of the chebyshev KSP with this prefix: out[0] emin and
  * [1] emax as used, [2] the smallest and [3] the largest real part of the
  * estimate's Hessenberg eigenvalues (NaN when the bounds were given with
@@ -340,11 +364,18 @@ int pls_anderson_destroy(pls_anderson *a);
  * y = A x on the handle's A, repeated `reps` times; returns the mean device
  * time per launch in seconds measured with HIP events on the solver stream. */
 int pls_bench_spmv(pls_handle *h, const double *d_x, double *d_y, int32_t reps, double *sec_per_launch);
+/* The same for the low-precision product of pls_matmult_single_device.      */
+int pls_bench_spmv_single(pls_handle *h, const double *d_x, double *d_y, int32_t reps, double *sec_per_launch);
 /* Layout of A's SpMV copy: d16 = 1 for SELL-64/D16 (16-bit column deltas),
  * 0 for SELL-64 (int32 columns); matrix_bytes = bytes one product streams
  * from the matrix arrays (padding included).  Option "pls.sell_d16 0"
  * forces the int32 layout.                                                   */
 int pls_spmv_layout(pls_handle *h, int32_t *d16, int64_t *matrix_bytes);
+/* The same for the low-precision product: d16 = 1 where A's layout can carry
+ * the fp32 value stream (SELL-64/D16 without a SELL/B3 part), matrix_bytes =
+ * bytes one low product streams, 4 B per stored entry for the values instead
+ * of 8 (0 where d16 = 0).                                                    */
+int pls_spmv_layout_single(pls_handle *h, int32_t *d16, int64_t *matrix_bytes);
 /* Streaming probe on the current device: per repetition `bytes` read (and,
  * unless read_only, `bytes` written) with 16-B-per-lane nontemporal accesses;
  * returns GB/s of bytes moved -- the achievable HBM rate beside the 8 TB/s

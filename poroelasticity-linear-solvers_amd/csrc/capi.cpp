@@ -71,6 +71,10 @@ struct Handle {
             ctx.d16_wide_lpr != 16 && ctx.d16_wide_lpr != 32 && ctx.d16_wide_lpr != 64)
             throw Error("pls.d16_wide_lpr must be a power of two <= 64");
         ctx.d16_unroll = (int)opt.integer("pls.d16_unroll", 4);
+        ctx.d16_unroll_single = (int)opt.integer("pls.d16_unroll_single", 8);  // the fp32-value kernel's depth
+        if (ctx.d16_unroll_single != 1 && ctx.d16_unroll_single != 2 && ctx.d16_unroll_single != 4 &&
+            ctx.d16_unroll_single != 8)
+            throw Error("pls.d16_unroll_single must be 1, 2, 4 or 8");
         ctx.halo_overlap = opt.flag("pls.halo_overlap", true);
         ctx.d16_segs = (int)opt.integer("pls.d16_segs", D16_SEG);  // 8: force the halo layout (tests)
         if (ctx.d16_segs != D16_SEG && ctx.d16_segs != D16_SEG_MAX) throw Error("pls.d16_segs must be 4 or 8");
@@ -223,6 +227,7 @@ static void do_setup_solver(Handle &H) {
                            &H.bpc);
         H.outer->owned_op.reset();
         H.outer->A = H.Aop.get();
+        if (H.outer->operator_single) H.Aop->enable_low(c, "global_pls_gmres_operator single");
         H.outer->monitor = H.outer->monitor || o.flag("pls.solver_monitor", false);
         const std::string gpc = o.str("global_pc_type", "python");
         if (gpc != "python") throw Error("global_pc_type must stay 'python' (the block preconditioner)");
@@ -254,6 +259,11 @@ static void decide_coupling(Handle &H) {
         R.reduced = DevSELL();
         R.why = why;
         if (mode == 1) throw Error("pls.reuse_coupling 1: the coupling product cannot be reused: " + why);
+    }
+    // compressed-operator GMRES: the fp32 streams of the (new) A and of its reduced layout
+    if (H.Aop && H.Aop->low) {
+        H.Aop->enable_low(H.ctx, "global_pls_gmres_operator single");
+        if (R.eligible) build_low(R.reduced, H.ctx, "global_pls_gmres_operator single (reduced outer operator)");
     }
     H.coupling_stale = false;
 }
@@ -512,6 +522,25 @@ int pls_matmult(pls_handle *hh, const double *x, double *y) {
     })
 }
 
+// the outer operator's layout with its fp32 value stream (built on demand; the refusals of build_low)
+static DevSELL &low_layout(Handle &H, const char *who) {
+    build_sell(H.A, H.ctx);
+    if (!H.A.sell) throw Error(std::string(who) + ": the operator has no rows");
+    build_low(*H.A.sell, H.ctx, who);
+    return *H.A.sell;
+}
+int pls_matmult_single(pls_handle *hh, const double *x, double *y) {
+    PLS_TRY({
+        Handle &H = *reinterpret_cast<Handle *>(hh);
+        DBuf<double> xi(H.n), yi(H.n);
+        if (!H.vout.p) H.vout.alloc(H.n);
+        to_internal(H, x, xi.p);
+        low_layout(H, "pls_matmult_single");
+        spmv(H.A, xi.p, yi.p, H.ctx, 1.0, 0.0, nullptr, true);
+        from_internal(H, yi.p, y);
+    })
+}
+
 int pls_solve(pls_handle *hh, const double *b, double *x, pls_result *res) {
     PLS_TRY({
         Handle &H = *reinterpret_cast<Handle *>(hh);
@@ -550,6 +579,17 @@ int pls_matmult_device(pls_handle *hh, const double *d_x, double *d_y) {
         // a PC application -- reduced when d_x is what pls_pc_apply_device returned last
         if (H.Aop && H.opt.flag("pls.reuse_coupling_probe", false)) H.Aop->apply_after(H.bpc, d_x, d_y, H.ctx);
         else spmv(H.A, d_x, d_y, H.ctx);
+        H.ctx.sync();
+    })
+}
+int pls_matmult_single_device(pls_handle *hh, const double *d_x, double *d_y) {
+    PLS_TRY({
+        Handle &H = *reinterpret_cast<Handle *>(hh);
+        low_layout(H, "pls_matmult_single_device");
+        // pls.reuse_coupling_probe (tests): as pls_matmult_device, through the low reduced launch
+        if (H.Aop && H.Aop->low && H.opt.flag("pls.reuse_coupling_probe", false))
+            H.Aop->apply_after_low(H.bpc, d_x, d_y, H.ctx);
+        else spmv(H.A, d_x, d_y, H.ctx, 1.0, 0.0, nullptr, true);
         H.ctx.sync();
     })
 }
@@ -665,6 +705,28 @@ int pls_get_gmres_basis_stats(pls_handle *hh, const char *prefix, int64_t *stats
         stats[4] = found->stat_cb_failed;
     })
 }
+int pls_get_gmres_operator_stats(pls_handle *hh, const char *prefix, int64_t *stats) {
+    PLS_TRY({
+        const KSP *found = find_ksp(*reinterpret_cast<Handle *>(hh), prefix, stats, "pls_get_gmres_operator_stats");
+        if (found->type != "gmres" && found->type != "fgmres")
+            throw Error("pls_get_gmres_operator_stats: the solver with prefix '" + found->prefix + "' is of type " +
+                        found->type + ", not gmres or fgmres");
+        const MatOp *op = dynamic_cast<const MatOp *>(found->A);
+        stats[0] = found->operator_single ? 1 : 0;
+        stats[1] = found->operator_single && op ? op->low_bytes() : 0;
+        stats[2] = found->stat_co_low;
+        stats[3] = found->stat_co_double;
+    })
+}
+int pls_get_reuse_rows(pls_handle *hh, uint8_t *mask) {
+    PLS_TRY({
+        Handle &H = *reinterpret_cast<Handle *>(hh);
+        if (!mask) throw Error("pls_get_reuse_rows: null argument");
+        const Coupling &R = H.coupling;
+        const bool on = R.eligible && (int64_t)R.reuse.size() == H.n;
+        for (int64_t i = 0; i < H.n; ++i) mask[H.perm[i]] = on ? R.reuse[i] : 0;
+    })
+}
 int pls_get_chebyshev_bounds(pls_handle *hh, const char *prefix, double *out) {
     PLS_TRY({
         const KSP *found = find_ksp(*reinterpret_cast<Handle *>(hh), prefix, out, "pls_get_chebyshev_bounds");
@@ -745,6 +807,26 @@ int pls_bench_spmv(pls_handle *hh, const double *d_x, double *d_y, int32_t reps,
         HIPCHK(hipEventCreate(&b));
         HIPCHK(hipEventRecord(a, H.ctx.st));
         for (int r = 0; r < reps; ++r) spmv(H.A, d_x, d_y, H.ctx);
+        HIPCHK(hipEventRecord(b, H.ctx.st));
+        HIPCHK(hipEventSynchronize(b));
+        float ms = 0.f;
+        HIPCHK(hipEventElapsedTime(&ms, a, b));
+        (void)hipEventDestroy(a);
+        (void)hipEventDestroy(b);
+        *sec_per_launch = (double)ms * 1e-3 / std::max(1, reps);
+    })
+}
+
+int pls_bench_spmv_single(pls_handle *hh, const double *d_x, double *d_y, int32_t reps, double *sec_per_launch) {
+    PLS_TRY({
+        Handle &H = *reinterpret_cast<Handle *>(hh);
+        H.A.tag = 1;
+        low_layout(H, "pls_bench_spmv_single");
+        hipEvent_t a, b;
+        HIPCHK(hipEventCreate(&a));
+        HIPCHK(hipEventCreate(&b));
+        HIPCHK(hipEventRecord(a, H.ctx.st));
+        for (int r = 0; r < reps; ++r) spmv(H.A, d_x, d_y, H.ctx, 1.0, 0.0, nullptr, true);
         HIPCHK(hipEventRecord(b, H.ctx.st));
         HIPCHK(hipEventSynchronize(b));
         float ms = 0.f;
@@ -923,6 +1005,16 @@ int pls_spmv_layout(pls_handle *hh, int32_t *d16, int64_t *matrix_bytes) {
         build_sell(H.A, H.ctx);
         if (d16) *d16 = H.A.sell && H.A.sell->d16 ? 1 : 0;
         if (matrix_bytes) *matrix_bytes = H.A.sell ? H.A.sell->bytes() : 0;
+    })
+}
+
+int pls_spmv_layout_single(pls_handle *hh, int32_t *d16, int64_t *matrix_bytes) {
+    PLS_TRY({
+        Handle &H = *reinterpret_cast<Handle *>(hh);
+        build_sell(H.A, H.ctx);
+        const bool ok = H.A.sell && H.A.sell->d16 && !H.A.sell->b3_nslices;
+        if (d16) *d16 = ok ? 1 : 0;
+        if (matrix_bytes) *matrix_bytes = ok ? H.A.sell->bytes_low() : 0;
     })
 }
 

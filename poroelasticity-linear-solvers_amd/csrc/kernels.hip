@@ -2982,6 +2982,165 @@ void launch_d16_spmv(int64_t nrows, int64_t nslices, const int64_t *sptr, const 
     else d16_unrolled<4>(unroll, g, st, nrows, nslices, sptr, sfirst, slpr, dl, dv, seg, x, y, alpha, beta, z, tag, ghost, nl, slist, rowmap, lds_reserve, aux_mode, aux);
 }
 
+// ------------------------------------------- D16 with fp32 values (low) ---
+// The low-precision operator of compressed-operator GMRES (pls_gmres_operator single): the
+// layout's deltas, bases and slices as they are, and a second value stream in fp32,
+//   values  dv32[base + (k / 4) * 256 + lane * 4 + k % 4]   (one float4 = 4 values)
+// so an 8-entry group is one delta load and two value loads of 16 B per lane, 6 B per entry.
+// k_d16_round_values fills it from the fp64 stream: every value rounded to nearest even once
+// (padding stays 0.0f).  A slice's base is a multiple of 512 entries, so the 256-entry blocks of
+// the two streams coincide and the copy needs no slice table: thread t writes float4 t from
+// double2 (t / 64) * 128 + t % 64 and the one 64 further.  *overflow = 1 when a finite value
+// rounds to an infinity.
+typedef float d16_f4 __attribute__((ext_vector_type(4)));
+__global__ __launch_bounds__(TPB) void k_d16_round_values(int64_t nquads, const double *__restrict__ dv,
+                                                          float *__restrict__ dv32, int32_t *overflow) {
+    const int64_t t = (int64_t)blockIdx.x * TPB + threadIdx.x;
+    if (t >= nquads) return;
+    const d16_d2 *src = reinterpret_cast<const d16_d2 *>(dv) + (t >> 6) * 128 + (t & 63);
+    const d16_d2 a = src[0], b = src[64];
+    d16_f4 f;
+    f.x = (float)a.x;
+    f.y = (float)a.y;
+    f.z = (float)b.x;
+    f.w = (float)b.y;
+    const bool bad = (isinf(f.x) && !isinf(a.x)) || (isinf(f.y) && !isinf(a.y)) || (isinf(f.z) && !isinf(b.x)) ||
+                     (isinf(f.w) && !isinf(b.y));
+    if (bad) *overflow = 1;
+    reinterpret_cast<d16_f4 *>(dv32)[t] = f;
+}
+void launch_d16_round_values(int64_t stored, const double *dv, float *dv32, int32_t *overflow, hipStream_t st) {
+    const int64_t nquads = stored / 4;  // stored is a multiple of 512
+    if (nquads > 0) k_d16_round_values<<<grid_for(nquads, TPB), TPB, 0, st>>>(nquads, dv, dv32, overflow);
+}
+
+// k_d16_spmv over the fp32 value stream: the same slice, lane and segment logic, x, every
+// product (double)a32 * x[col] and every sum in fp64 and in the same order.  AUX: none, or
+// D16_AUX_INIT (the reduced outer launch; the raw sums the PC stored are fp64).
+template <int G2, int TAG, bool HALO, int SEG, int AUX = D16_AUX_NONE>
+__global__ __launch_bounds__(TPB) void k_d16_spmv_f32(int64_t nrows, int64_t nslices, const int64_t *__restrict__ sptr,
+                                                      const int64_t *__restrict__ sfirst,
+                                                      const int32_t *__restrict__ slpr,
+                                                      const uint16_t *__restrict__ dl, const float *__restrict__ dv32,
+                                                      const int32_t *__restrict__ seg, const double *__restrict__ x,
+                                                      double *__restrict__ y, double alpha, double beta,
+                                                      const double *__restrict__ z, const double *__restrict__ ghost,
+                                                      int32_t nlocal, const int32_t *__restrict__ slist,
+                                                      const int32_t *__restrict__ rowmap, const double *aux) {
+    static_assert(SEG == 4 || SEG == 8, "segment bases are one or two int4 per lane");
+    static_assert(AUX == D16_AUX_NONE || AUX == D16_AUX_INIT, "the raw-sum store belongs to the fp64 launch");
+    const int lane = threadIdx.x & 63;
+    unsigned blk = blockIdx.x;
+    if (d16_xcd_map) {
+        const unsigned per = (gridDim.x + 7) / 8;
+        blk = (blockIdx.x % 8) * per + blockIdx.x / 8;
+    }
+    const int64_t idx = __builtin_amdgcn_readfirstlane((int)(blk * (TPB / 64) + (threadIdx.x >> 6)));
+    if (idx >= nslices) return;
+    const int64_t sl = slist ? (int64_t)__builtin_amdgcn_readfirstlane(slist[idx]) : idx;
+    const int64_t base = sptr[sl];
+    const int64_t L = (sptr[sl + 1] - base) >> 6;  // multiple of 8
+    const int lpr = slpr[sl];
+    const int64_t r0 = sfirst[sl], r1 = sfirst[sl + 1];
+    const int64_t row = r0 + lane / lpr;
+    const d16_i4 sb = __builtin_nontemporal_load(reinterpret_cast<const d16_i4 *>(seg) + (sl * 64 + lane) * (SEG / 4));
+    d16_i4 sb2 = sb;
+    if (SEG == 8) sb2 = __builtin_nontemporal_load(reinterpret_cast<const d16_i4 *>(seg) + (sl * 64 + lane) * 2 + 1);
+    const d16_u4 *dp = reinterpret_cast<const d16_u4 *>(dl + base) + lane;
+    const d16_f4 *vp = reinterpret_cast<const d16_f4 *>(dv32 + base) + lane;
+    int32_t col = 0;
+    int si = 0;
+    double acc = 0.0;
+    if (AUX == D16_AUX_INIT && lpr == 1 && row < r1) acc = aux[row];
+    const int64_t ng = L >> 3;
+    for (int64_t g0 = 0; g0 < ng; g0 += G2) {
+        d16_u4 d[G2];
+        d16_f4 v[G2][2];
+#pragma unroll
+        for (int u = 0; u < G2; ++u) {
+            const int64_t g = g0 + u < ng ? g0 + u : ng - 1;  // wave-uniform clamp, values masked
+            d[u] = __builtin_nontemporal_load(dp + g * 64);
+#pragma unroll
+            for (int q = 0; q < 2; ++q) v[u][q] = __builtin_nontemporal_load(vp + (g * 2 + q) * 64);
+        }
+#pragma unroll
+        for (int u = 0; u < G2; ++u) {
+            if (g0 + u >= ng) break;
+            const uint32_t w[4] = {d[u].x, d[u].y, d[u].z, d[u].w};
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const int32_t dd = (int32_t)((w[e >> 1] >> ((e & 1) * 16)) & 0xffffu);
+                int32_t b = si == 0 ? sb.x : si == 1 ? sb.y : si == 2 ? sb.z : sb.w;
+                if (SEG == 8 && si >= 4) b = si == 4 ? sb2.x : si == 5 ? sb2.y : si == 6 ? sb2.z : sb2.w;
+                col = dd == 0 ? b : col + dd;
+                si += dd == 0 ? 1 : 0;
+                const d16_f4 vq = v[u][e >> 2];
+                const double a = (double)((e & 3) == 0 ? vq.x : (e & 3) == 1 ? vq.y : (e & 3) == 2 ? vq.z : vq.w);
+                if (HALO) {
+                    const bool loc = col < nlocal;
+                    const double xv = loc ? x[(uint32_t)col] : ghost[(uint32_t)(col - nlocal)];
+                    acc += a * xv;
+                } else {
+                    acc += a * x[(uint32_t)col];
+                }
+            }
+        }
+    }
+    if (lpr > 1) {  // wave-uniform: combine the LPR partial sums of a row
+        for (int o = 1; o < lpr; o <<= 1) acc += __shfl_xor(acc, o);
+        if (lane % lpr) return;
+    }
+    if (row < r1) {
+        const int64_t yr = rowmap ? (int64_t)rowmap[row] : row;
+        double r = alpha * acc;
+        if (beta != 0.0) r += beta * z[yr];
+        y[yr] = r;
+    }
+}
+#define D16_F32_ARGS nrows, ns, sptr, sfirst, slpr, dl, dv32, seg, x, y, alpha, beta, z, ghost, nl, slist, rm, aux
+template <int G2, int SEG>
+static void d16_f32_dispatch(unsigned g, hipStream_t st, int64_t nrows, int64_t ns, const int64_t *sptr,
+                             const int64_t *sfirst, const int32_t *slpr, const uint16_t *dl, const float *dv32,
+                             const int32_t *seg, const double *x, double *y, double alpha, double beta,
+                             const double *z, int tag, const double *ghost, int32_t nl, const int32_t *slist,
+                             const int32_t *rm, size_t shm, const double *aux) {
+    if (aux) {  // the reduced outer launch (tag 1, one rank, plain layout: MatOp::apply_after_low)
+        k_d16_spmv_f32<G2, 1, false, SEG, D16_AUX_INIT><<<g, TPB, shm, st>>>(D16_F32_ARGS);
+    } else if (ghost) {
+        if (tag) k_d16_spmv_f32<G2, 1, true, SEG><<<g, TPB, shm, st>>>(D16_F32_ARGS);
+        else k_d16_spmv_f32<G2, 0, true, SEG><<<g, TPB, shm, st>>>(D16_F32_ARGS);
+    } else {
+        if (tag) k_d16_spmv_f32<G2, 1, false, SEG><<<g, TPB, shm, st>>>(D16_F32_ARGS);
+        else k_d16_spmv_f32<G2, 0, false, SEG><<<g, TPB, shm, st>>>(D16_F32_ARGS);
+    }
+}
+#undef D16_F32_ARGS
+template <int SEG>
+static void d16_f32_unrolled(int unroll, unsigned g, hipStream_t st, int64_t nrows, int64_t ns, const int64_t *sptr,
+                             const int64_t *sfirst, const int32_t *slpr, const uint16_t *dl, const float *dv32,
+                             const int32_t *seg, const double *x, double *y, double alpha, double beta,
+                             const double *z, int tag, const double *ghost, int32_t nl, const int32_t *slist,
+                             const int32_t *rm, size_t shm, const double *aux) {
+    switch (unroll) {
+        case 1: d16_f32_dispatch<1, SEG>(g, st, nrows, ns, sptr, sfirst, slpr, dl, dv32, seg, x, y, alpha, beta, z, tag, ghost, nl, slist, rm, shm, aux); break;
+        case 2: d16_f32_dispatch<2, SEG>(g, st, nrows, ns, sptr, sfirst, slpr, dl, dv32, seg, x, y, alpha, beta, z, tag, ghost, nl, slist, rm, shm, aux); break;
+        case 4: d16_f32_dispatch<4, SEG>(g, st, nrows, ns, sptr, sfirst, slpr, dl, dv32, seg, x, y, alpha, beta, z, tag, ghost, nl, slist, rm, shm, aux); break;
+        default: d16_f32_dispatch<8, SEG>(g, st, nrows, ns, sptr, sfirst, slpr, dl, dv32, seg, x, y, alpha, beta, z, tag, ghost, nl, slist, rm, shm, aux); break;
+    }
+}
+void launch_d16_spmv_f32(int64_t nrows, int64_t nslices, const int64_t *sptr, const int64_t *sfirst,
+                         const int32_t *slpr, const uint16_t *dl, const float *dv32, const int32_t *seg, int nsegs,
+                         const double *x, double *y, double alpha, double beta, const double *z, int tag,
+                         const double *ghost, int64_t nlocal, int unroll, hipStream_t st, const int32_t *slist,
+                         const int32_t *rowmap, size_t lds_reserve, const double *aux_init) {
+    if (nslices <= 0) return;
+    unsigned g = grid_for(nslices, TPB / 64);
+    if (d16_xcd_host) g = (g + 7) / 8 * 8;
+    const int32_t nl = (int32_t)nlocal;
+    if (nsegs == 8) d16_f32_unrolled<8>(unroll, g, st, nrows, nslices, sptr, sfirst, slpr, dl, dv32, seg, x, y, alpha, beta, z, tag, ghost, nl, slist, rowmap, lds_reserve, aux_init);
+    else d16_f32_unrolled<4>(unroll, g, st, nrows, nslices, sptr, sfirst, slpr, dl, dv32, seg, x, y, alpha, beta, z, tag, ghost, nl, slist, rowmap, lds_reserve, aux_init);
+}
+
 // ============================================================ SELL/B3 ======
 // Row triples of FE vector fields: the 3 components of a P2 node have the same
 // sparsity pattern, so a triple shares one column list.  B3_LPT lanes per

@@ -295,6 +295,18 @@ void launch_d16_spmv(int64_t nrows, int64_t nslices, const int64_t *sptr, const 
                      size_t lds_reserve = 0 /* dynamic LDS per workgroup, unused: keeps the product's
                                                workgroups off CUs whose LDS a sweep holds */,
                      int aux_mode = D16_AUX_NONE, double *aux = nullptr /* nrows: raw row sums, see D16_AUX_* */);
+// Compressed-operator GMRES (pls_gmres_operator single): a D16 layout's values once more in fp32,
+// dv32[base + (k / 4) * 256 + lane * 4 + k % 4], rounded to nearest even from the fp64 stream
+// (stored: the layout's padded entries; *overflow = 1 when a finite value rounds to an infinity) ...
+void launch_d16_round_values(int64_t stored, const double *dv, float *dv32, int32_t *overflow, hipStream_t st);
+// ... and launch_d16_spmv over that stream: x, products and sums fp64, in the same order.
+// unroll: 1, 2, 4 or 8; aux_init != null: D16_AUX_INIT (plain layouts on one rank, tag 1)
+void launch_d16_spmv_f32(int64_t nrows, int64_t nslices, const int64_t *sptr, const int64_t *sfirst,
+                         const int32_t *slpr, const uint16_t *dl, const float *dv32, const int32_t *seg, int nsegs,
+                         const double *x, double *y, double alpha, double beta, const double *z, int tag,
+                         const double *ghost, int64_t nlocal, int unroll, hipStream_t st,
+                         const int32_t *slist = nullptr, const int32_t *rowmap = nullptr, size_t lds_reserve = 0,
+                         const double *aux_init = nullptr);
 // SELL/B3: row triples sharing one column list (FE vector fields), see kernels.hip
 void launch_triple_flags(int64_t n, const int64_t *rp, const int32_t *ci, uint8_t *flag, hipStream_t st);
 int b3_lanes_per_triple();

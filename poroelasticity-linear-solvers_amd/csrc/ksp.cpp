@@ -314,6 +314,7 @@ void KSP::guess_update(const double *x, Ctx &c) {
     }
     double *y = gy.p, *d = gd.p;
     A->apply(x, y, c);
+    if (basis_single) ++stat_co_double;  // (the guess products stay fp64)
     auto read_back = [&](int count) {
         double *hs = c.host_scalars(count);
         HIPCHK(hipMemcpyAsync(hs, d, sizeof(double) * count, hipMemcpyDeviceToHost, c.st));
@@ -350,6 +351,7 @@ void KSP::guess_update(const double *x, Ctx &c) {
             // (7e-11 at nu = 1e-6 nu0): B's column is formed again as the product A x', projected once more
             // (the new column is orthogonal to the others to eps nu0 / nu only) and normalised again
             A->apply(xo, yo, c);
+            if (basis_single) ++stat_co_double;  // (the guess products stay fp64)
             launch_mdot(n, m, nullptr, gB.p, guess_ldv, yo, c.partials(n, m), beta, c.st);
             c.comm->global_sum_dev(beta, m, c.st);
             launch_guess_update(n, m, gX.p, gB.p, guess_ldv, beta, nullptr, nullptr, c.partials(n, 1), d + m + 1,
@@ -377,6 +379,7 @@ void KSP::solve_guessed(const double *b, double *x, Ctx &c) {
         launch_copy(n, x, x0, c.st);
     }
     A->residual(x0, b, r0, c);
+    if (basis_single) ++stat_co_double;  // (the guess products stay fp64)
     const bool pnorm = norm == "preconditioned";
     launch_dot(n, b, b, c.partials(n, 1), d, c.st);
     launch_dot(n, r0, r0, c.partials(n, 1), d + 1, c.st);
@@ -637,6 +640,11 @@ void KSP::solve_gmres_cb(const double *b, double *x, Ctx &c) {
         nrs(mk + 1, 0.0), hcol(mk + 1, 0.0);
     auto H = [&](int64_t i, int64_t j) -> double & { return HH[(size_t)i * (mk + 1) + j]; };
     double *w = cbw.p, *vd = cbv.p, *t1p = t1.p, *t2p = t2.p;
+    // compressed operator: the Arnoldi products through the fp32 copy of A, a cycle being one step
+    // of iterative refinement that the fp64 residual below corrects
+    const bool low = operator_single;
+    if (low && !A->has_low())
+        throw Error(prefix + "pls_gmres_operator single: the operator of this solver is not a stored matrix");
     launch_set(n, 0.0, x, c.st);
     its = 0;
     reason = 0;
@@ -646,6 +654,7 @@ void KSP::solve_gmres_cb(const double *b, double *x, Ctx &c) {
             launch_copy(n, b, right ? w : t1p, c.st);
         } else {
             A->apply(x, t2p, c);
+            ++stat_co_double;
             launch_waxpby(n, 1.0, b, -1.0, t2p, right ? w : t1p, c.st);
         }
         if (!right) pc->apply(t1p, w, c);
@@ -679,11 +688,14 @@ void KSP::solve_gmres_cb(const double *b, double *x, Ctx &c) {
             if (right) {
                 double *zk = flexible ? Z.p + loc_it * ldv : t1p;
                 pc->apply(vd, zk, c);
-                A->apply_after(*pc, zk, w, c);
+                if (low) A->apply_after_low(*pc, zk, w, c);
+                else A->apply_after(*pc, zk, w, c);
             } else {
-                A->apply(vd, t1p, c);
+                if (low) A->apply_low(vd, t1p, c);
+                else A->apply(vd, t1p, c);
                 pc->apply(t1p, w, c);
             }
+            ++(low ? stat_co_low : stat_co_double);
             const int k = (int)(loc_it + 1);
             const double tt = std::sqrt(gmres_orthogonalise_cb(k, w, hcol.data(), c));
             for (int j = 0; j < k; ++j) H(j, loc_it) = hcol[j];
@@ -1390,6 +1402,14 @@ std::unique_ptr<KSP> make_ksp(const std::string &prefix, const Options &o, const
         if (k->basis_single && k->orthog == KSP::MGS && k->mgs_fused)
             throw Error(bkey + " single is not available together with pls.gmres_mgs_fused 1 (" + prefix +
                         "ksp_gmres_modifiedgramschmidt): the fp32 step kernel has no single-launch sums");
+        // the precision of the operator inside the Arnoldi step (the fp32 basis' cycle only)
+        const std::string okey = prefix + "pls_gmres_operator", oper = o.str(okey, "double");
+        if (oper != "double" && oper != "single")
+            throw Error(okey + ": unknown value '" + oper + "' (double, single)");
+        if (oper == "single" && !k->basis_single)
+            throw Error(okey + " single requires " + bkey + " single: the low-precision operator runs inside the " +
+                        "compressed-basis cycle, whose true residuals correct it");
+        k->operator_single = oper == "single";
     }
     k->resolve_side_norm(o.str(prefix + "ksp_pc_side", ""), o.str(prefix + "ksp_norm_type", ""));
     {
@@ -1461,9 +1481,13 @@ std::unique_ptr<KSP> make_ksp(const std::string &prefix, const Options &o, const
             throw Error(who + prefix + "ksp_chebyshev_esteig_steps must be between 1 and 64");
     }
     if (Amat) {
-        k->owned_op = std::make_unique<MatOp>(Amat);
+        auto op = std::make_unique<MatOp>(Amat);
+        if (k->operator_single) op->enable_low(c, prefix + "pls_gmres_operator single");
+        k->owned_op = std::move(op);
         k->A = k->owned_op.get();
         k->n = Amat->nrows;
+    } else if (k->operator_single) {
+        throw Error(prefix + "pls_gmres_operator single: the operator of this solver is not a stored matrix");
     }
     if (external_pc) {
         k->pc = external_pc;

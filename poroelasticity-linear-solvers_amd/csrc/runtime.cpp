@@ -600,9 +600,44 @@ void classify_halo_slices(DevCSR &M, Ctx &c) {
     c.sync();
 }
 
-void spmv(const DevCSR &M, const double *x, double *y, Ctx &c, double alpha, double beta, const double *z) {
+void build_low(DevSELL &S, Ctx &c, const std::string &who) {
+    if (!S.d16)
+        throw Error(who + ": the operator's SpMV layout is " + (S.col.p ? "int32 SELL-64" : "CSR") +
+                    ", not SELL-64/D16 (no fp32 value stream for it)");
+    if (S.b3_nslices)
+        throw Error(who + ": the operator's SpMV layout has a SELL/B3 part (pls.spmv_b3): no fp32 value stream for it");
+    if (S.val32.p) return;
+    S.val32.alloc(std::max<int64_t>(S.stored, 4));
+    DBuf<int32_t> over(1);
+    HIPCHK(hipMemsetAsync(over.p, 0, sizeof(int32_t), c.st));
+    launch_d16_round_values(S.stored, S.val.p, S.val32.p, over.p, c.st);
+    HIPCHK(hipGetLastError());
+    int32_t h = 0;
+    HIPCHK(hipMemcpyAsync(&h, over.p, sizeof(int32_t), hipMemcpyDeviceToHost, c.st));
+    c.sync();
+    if (h) {
+        S.val32.release();
+        throw Error(who + ": a finite matrix value is infinite once rounded to fp32 (|a| > 3.4028235e38)");
+    }
+}
+
+// the D16 launch of spmv(): over the fp64 value stream, or (low) over the fp32 one
+static void d16_product(const DevCSR &M, const DevSELL &S, int64_t count, const int32_t *slist, const double *x,
+                        double *y, double alpha, double beta, const double *z, const double *ghost, int64_t nlocal,
+                        Ctx &c, bool low) {
+    const int32_t *rm = S.nrows_mapped ? S.rowmap.p : nullptr;
+    if (low)
+        launch_d16_spmv_f32(M.nrows, count, S.sptr.p, S.sfirst.p, S.slpr.p, S.dl.p, S.val32.p, S.seg.p, S.nsegs, x, y,
+                            alpha, beta, z, M.tag, ghost, nlocal, c.d16_unroll_single, c.st, slist, rm);
+    else
+        launch_d16_spmv(M.nrows, count, S.sptr.p, S.sfirst.p, S.slpr.p, S.dl.p, S.val.p, S.seg.p, S.nsegs, x, y, alpha,
+                        beta, z, M.tag, ghost, nlocal, c.d16_unroll, c.st, slist, rm);
+}
+
+void spmv(const DevCSR &M, const double *x, double *y, Ctx &c, double alpha, double beta, const double *z, bool low) {
     const double *ghost = nullptr;
     int64_t nlocal = M.ncols;
+    if (low && !(M.sell && M.sell->has_low())) throw Error("spmv: the matrix has no fp32 value stream (build_low)");
     if (M.halo && c.halo_overlap && M.sell && M.sell->d16 && M.sell->n_halo + M.sell->n_in == M.sell->nslices) {
         // interior slices on the solver stream while the pack + exchange run on
         // the comm stream; the halo slices after the exchange.  Per-row sums
@@ -619,16 +654,12 @@ void spmv(const DevCSR &M, const double *x, double *y, Ctx &c, double alpha, dou
         }
         HIPCHK(hipEventRecord(c.ev_x, c.st));
         HIPCHK(hipStreamWaitEvent(c.st_comm, c.ev_x, 0));
-        launch_d16_spmv(M.nrows, S.n_in, S.sptr.p, S.sfirst.p, S.slpr.p, S.dl.p, S.val.p, S.seg.p, S.nsegs, x, y,
-                        alpha, beta, z, M.tag, nullptr, H.nlocal, c.d16_unroll, c.st, S.s_in.p,
-                        S.nrows_mapped ? S.rowmap.p : nullptr);
+        d16_product(M, S, S.n_in, S.s_in.p, x, y, alpha, beta, z, nullptr, H.nlocal, c, low);
         launch_pack(H.nsend, H.send_idx.p, x, H.sendbuf.p, c.st_comm);
         c.comm->exchange_dev(H.sendbuf.p, H.scnt, H.soff, H.ghost.p, H.rcnt, H.roff, c.st_comm);
         HIPCHK(hipEventRecord(c.ev_halo, c.st_comm));
         HIPCHK(hipStreamWaitEvent(c.st, c.ev_halo, 0));
-        launch_d16_spmv(M.nrows, S.n_halo, S.sptr.p, S.sfirst.p, S.slpr.p, S.dl.p, S.val.p, S.seg.p, S.nsegs, x, y,
-                        alpha, beta, z, M.tag, H.ghost.p, H.nlocal, c.d16_unroll, c.st, S.s_halo.p,
-                        S.nrows_mapped ? S.rowmap.p : nullptr);
+        d16_product(M, S, S.n_halo, S.s_halo.p, x, y, alpha, beta, z, H.ghost.p, H.nlocal, c, low);
         return;
     }
     if (M.halo) {
@@ -652,9 +683,7 @@ void spmv(const DevCSR &M, const double *x, double *y, Ctx &c, double alpha, dou
         if (S.b3_nslices)
             launch_b3_spmv(S.b3_nslices, S.b3_ntrip, S.b3ptr.p, S.b3map.p, S.b3col.p, S.b3val.p, x, y, alpha, beta, z,
                            M.tag, c.st);
-        launch_d16_spmv(M.nrows, S.nslices, S.sptr.p, S.sfirst.p, S.slpr.p, S.dl.p, S.val.p, S.seg.p, S.nsegs, x, y, alpha,
-                        beta, z, M.tag, ghost, nlocal, c.d16_unroll, c.st, nullptr,
-                        S.nrows_mapped ? S.rowmap.p : nullptr);
+        d16_product(M, S, S.nslices, nullptr, x, y, alpha, beta, z, ghost, nlocal, c, low);
         return;
     }
     if (M.sell) {
@@ -695,6 +724,7 @@ bool build_coupling(const DevCSR &A, int64_t ns, const DevCSR &M, Coupling &R, C
     R.fresh_for = nullptr;
     R.reduced = DevSELL();
     R.reuse_rows = 0;
+    R.reuse.clear();
     const int64_t n = A.nrows;
     if (!plain_d16(A) || !plain_d16(M)) {
         R.why = "the outer operator's or the coupling block's layout is not plain D16";
@@ -750,6 +780,7 @@ bool build_coupling(const DevCSR &A, int64_t ns, const DevCSR &M, Coupling &R, C
     HIPCHK(hipMemsetAsync(R.q.p, 0, sizeof(double) * n, c.st));
     c.sync();
     R.why.clear();
+    R.reuse = std::move(reuse);
     R.eligible = true;
     return true;
 }
@@ -862,6 +893,53 @@ void MatOp::apply_after(const PC &pc, const double *x, double *y, Ctx &c) {
     if (timers) timers->begin(T_SPMV);
     launch_d16_spmv(M->nrows, S.nslices, S.sptr.p, S.sfirst.p, S.slpr.p, S.dl.p, S.val.p, S.seg.p, S.nsegs, x, y, 1.0,
                     0.0, nullptr, 1, nullptr, M->ncols, c.d16_unroll, c.st, nullptr, nullptr, 0, D16_AUX_INIT, R->q.p);
+    if (timers) {
+        timers->end(T_SPMV);
+        timers->spmv_calls++;
+        if (R->spans_flush == timers->flushes)
+            for (const Timers::Span &sp : R->spans) timers->add(T_SPMV, sp);
+    }
+    R->spans.clear();
+    R->n_reduced++;
+}
+
+// ---- the low-precision operator (compressed-operator GMRES)
+void Op::apply_low(const double *, double *, Ctx &) {
+    throw Error("this operator has no low-precision copy (pls_gmres_operator single needs a stored matrix)");
+}
+void Op::apply_after_low(const PC &, const double *x, double *y, Ctx &c) { apply_low(x, y, c); }
+
+void MatOp::enable_low(Ctx &c, const std::string &who) {
+    low = true;
+    if (!M->sell) build_sell(const_cast<DevCSR &>(*M), c);
+    if (!M->sell) throw Error(who + ": the operator has no rows");
+    build_low(*M->sell, c, who);
+}
+int64_t MatOp::low_bytes() const {
+    return (M->sell ? M->sell->low_stream_bytes() : 0) +
+           (coupling && coupling->eligible ? coupling->reduced.low_stream_bytes() : 0);
+}
+void MatOp::apply_low(const double *x, double *y, Ctx &c) {
+    if (!low) throw Error("MatOp::apply_low: the low-precision operator was not asked for");
+    if (!M->sell || !M->sell->has_low()) enable_low(c, "pls_gmres_operator single");  // (a new layout: the matrix changed)
+    if (timers) timers->begin(T_SPMV);
+    spmv(*M, x, y, c, 1.0, 0.0, nullptr, true);
+    if (timers) { timers->end(T_SPMV); timers->spmv_calls++; }
+    if (coupling) coupling->n_full++;
+}
+// apply_after over the fp32 stream of A': the reuse rows start from the PC's fp64 raw sums, so
+// their coupling entries enter with their fp64 values
+void MatOp::apply_after_low(const PC &pc, const double *x, double *y, Ctx &c) {
+    Coupling *R = coupling;
+    if (!R || !R->eligible || pc.coupling_product() != R || R->fresh_for != x) return apply_low(x, y, c);
+    if (!low) throw Error("MatOp::apply_after_low: the low-precision operator was not asked for");
+    if (!R->reduced.has_low()) build_low(R->reduced, c, "pls_gmres_operator single (reduced outer operator)");
+    R->fresh_for = nullptr;
+    const DevSELL &S = R->reduced;
+    if (timers) timers->begin(T_SPMV);
+    launch_d16_spmv_f32(M->nrows, S.nslices, S.sptr.p, S.sfirst.p, S.slpr.p, S.dl.p, S.val32.p, S.seg.p, S.nsegs, x, y,
+                        1.0, 0.0, nullptr, 1, nullptr, M->ncols, c.d16_unroll_single, c.st, nullptr, nullptr, 0,
+                        R->q.p);
     if (timers) {
         timers->end(T_SPMV);
         timers->spmv_calls++;
@@ -1223,6 +1301,7 @@ std::unique_ptr<Ctx> layout_ctx(const Ctx &c) {
     self->sell_d16 = c.sell_d16;
     self->d16_wide_lpr = c.d16_wide_lpr;
     self->d16_unroll = c.d16_unroll;
+    self->d16_unroll_single = c.d16_unroll_single;
     self->d16_segs = c.d16_segs;
     self->d16_sigma = c.d16_sigma;
     self->d16_sigma_pad = c.d16_sigma_pad;

@@ -75,6 +75,7 @@ struct Ctx {
     bool sell_d16 = true;     // build SpMV layouts as SELL-64/D16 where every row fits
     int d16_wide_lpr = 8;     // lanes per row of D16 slices with wide rows (option pls.d16_wide_lpr)
     int d16_unroll = 4;       // D16 SpMV 8-entry groups per lane in flight (option pls.d16_unroll)
+    int d16_unroll_single = 8;  // ... of the fp32-value kernel: 1, 2, 4 or 8 (option pls.d16_unroll_single)
     int d16_segs = D16_SEG;   // minimum D16 segment bases per lane (option pls.d16_segs; 8 where needed)
     int d16_sigma = 1024;         // SELL-C-sigma window (rows sorted by length; 0: never) (pls.d16_sigma)
     double d16_sigma_pad = 0.15;  // ... used when the plain plan pads more than this fraction (pls.d16_sigma_pad)
@@ -162,6 +163,12 @@ struct DevSELL {
     // xp = x[xperm] (Ctx::rcm_x) so a slice's gathers stay local
     int64_t nperm = 0;
     DBuf<int32_t> xperm;
+    // Compressed-operator GMRES (pls_gmres_operator single): the D16 values once more, rounded to
+    // fp32, val32[base + (k / 4) * 256 + lane * 4 + k % 4] (build_low; empty until a KSP asks)
+    DBuf<float> val32;
+    bool has_low() const { return d16 && !b3_nslices && val32.p != nullptr; }
+    int64_t low_stream_bytes() const { return has_low() ? stored * 4 : 0; }
+    int64_t bytes_low() const { return bytes() - stored * 4; }  // bytes one low product streams (D16 only)
     int64_t bytes() const {  // bytes one product streams from the matrix
         return (d16 ? stored * 10 + nslices * (64 * 4 * nsegs + 20) + 8 + nrows_mapped * 4
                     : stored * 12 + (nslices + 1) * 8) +
@@ -205,8 +212,13 @@ void extract_csr(const DevCSR &src, int64_t r0, int64_t r1, WindowSpec w, int64_
 // product overlaps the halo exchange with the interior slices).  build_sell
 // calls it for matrices with a halo.
 void classify_halo_slices(DevCSR &M, Ctx &c);
+// low: the D16 kernel over the layout's fp32 value stream (build_low first), x and sums fp64
 void spmv(const DevCSR &M, const double *x, double *y, Ctx &c, double alpha = 1.0, double beta = 0.0,
-          const double *z = nullptr);
+          const double *z = nullptr, bool low = false);
+// The fp32 value stream of a D16 layout, from its fp64 stream on the device (a no-op when it
+// exists).  Throws, naming `who` and the condition, when the layout is not SELL-64/D16, has a B3
+// part, or holds a finite value whose fp32 rounding is infinite.
+void build_low(DevSELL &S, Ctx &c, const std::string &who);
 // qout (plain D16 layouts): also qout[row] = the raw row sum, before alpha and beta, for the
 // rows of lane-per-row slices (launch_d16_spmv's D16_AUX_STORE)
 void spmv_slices(const DevCSR &M, const double *x, double *y, Ctx &c, double alpha, double beta, const double *z,
@@ -319,6 +331,7 @@ struct Coupling {
     std::string why;           // ... and why not
     DevSELL reduced;           // second D16 layout of the outer operator (A's slice plan)
     int64_t reuse_rows = 0;
+    std::vector<uint8_t> reuse;  // per row (internal order): 1 on the reuse rows (empty: not eligible)
     DBuf<double> q;            // n: raw sums on the reuse rows; zero wherever the reduced launch reads it else
     const double *fresh_for = nullptr;  // the z the PC returned last, while q belongs to it
     std::vector<Timers::Span> spans;    // the PC's coupling launches of that application
@@ -340,6 +353,11 @@ struct Op {
     virtual void apply_after(const PC &pc, const double *x, double *y, Ctx &c) { apply(x, y, c); }
     // r = b - A x (r is neither x nor b); a matrix does it in the product's launch
     virtual void residual(const double *x, const double *b, double *r, Ctx &c);
+    // Compressed-operator GMRES: y = A^ x with the operator's low-precision copy (MatOp: the
+    // stored values rounded to fp32 once; x, y and every sum fp64), and its apply_after
+    virtual bool has_low() const { return false; }
+    virtual void apply_low(const double *x, double *y, Ctx &c);
+    virtual void apply_after_low(const PC &pc, const double *x, double *y, Ctx &c);
 };
 struct MatOp : Op {
     const DevCSR *M;
@@ -350,6 +368,14 @@ struct MatOp : Op {
     void apply(const double *x, double *y, Ctx &c) override;
     void apply_after(const PC &pc, const double *x, double *y, Ctx &c) override;
     void residual(const double *x, const double *b, double *r, Ctx &c) override;
+    // low: a KSP with pls_gmres_operator single uses this operator (enable_low: the layout and its
+    // fp32 stream now, with the refusals; after a matrix update the streams are rebuilt on demand)
+    bool low = false;
+    void enable_low(Ctx &c, const std::string &who);
+    bool has_low() const override { return low; }
+    void apply_low(const double *x, double *y, Ctx &c) override;
+    void apply_after_low(const PC &pc, const double *x, double *y, Ctx &c) override;
+    int64_t low_bytes() const;  // bytes of the fp32 streams held: the layout's and the coupling's reduced one
 };
 
 // --------------------------------------------------------- preconditioners --
@@ -497,6 +523,11 @@ struct KSP {
     bool vf_canary = false;     // pls.debug_bounds: Ctx::CANARY guard bytes behind Vf (check_basis_bounds)
     int64_t stat_cb_forced = 0, stat_cb_confirm = 0, stat_cb_failed = 0;  // rule (a) cycle ends, rule (b)
                                                                           // confirmations, those that failed
+    // Compressed-operator GMRES (<prefix>pls_gmres_operator single, with the fp32 basis only): the
+    // Arnoldi step's product through A->apply_low / apply_after_low; cycle-start residuals, the
+    // guesses' products and everything else through the fp64 operator
+    bool operator_single = false;
+    int64_t stat_co_low = 0, stat_co_double = 0;  // low / fp64 products in solves
     int64_t basis_bytes() const { return basis_single ? (int64_t)(Vf.n * sizeof(float)) : (int64_t)(V.n * sizeof(double)); }
     // GMRES: keep the Hessenberg columns of the first cycle as Arnoldi made them (the cycle
     // rotates its own copy in place): hess[i + j * (restart + 1)], column j = step j

@@ -50,6 +50,8 @@ EXPORTS = [
     "pls_get_ksp_stats", "pls_get_gmres_orthog_stats", "pls_get_chebyshev_bounds",
     "pls_hessenberg_eigenvalues", "pls_get_reuse_stats", "pls_get_ilu_fill",
     "pls_get_gmres_basis_stats", "pls_get_ksp_guess_stats", "pls_get_ksp_guess_info",
+    "pls_matmult_single", "pls_matmult_single_device", "pls_spmv_layout_single", "pls_bench_spmv_single",
+    "pls_get_gmres_operator_stats", "pls_get_reuse_rows",
 ]
 
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p)
@@ -92,6 +94,12 @@ def lib():
     L.pls_get_ksp_stats.argtypes = [vp, C.c_char_p, vp]
     L.pls_get_gmres_orthog_stats.argtypes = [vp, C.c_char_p, vp]
     L.pls_get_gmres_basis_stats.argtypes = [vp, C.c_char_p, vp]
+    L.pls_get_gmres_operator_stats.argtypes = [vp, C.c_char_p, vp]
+    L.pls_get_reuse_rows.argtypes = [vp, vp]
+    L.pls_matmult_single.argtypes = [vp, vp, vp]
+    L.pls_matmult_single_device.argtypes = [vp, vp, vp]
+    L.pls_bench_spmv_single.argtypes = [vp, vp, vp, i32, C.POINTER(C.c_double)]
+    L.pls_spmv_layout_single.argtypes = [vp, C.POINTER(i32), C.POINTER(i64)]
     L.pls_get_ksp_guess_stats.argtypes = [vp, C.c_char_p, vp, C.POINTER(C.c_double)]
     L.pls_get_ksp_guess_info.argtypes = [vp, C.c_char_p, C.POINTER(i64), C.POINTER(C.c_double)]
     L.pls_get_chebyshev_bounds.argtypes = [vp, C.c_char_p, vp]

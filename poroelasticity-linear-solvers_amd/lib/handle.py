@@ -163,6 +163,14 @@ class Handle:
         N.check(N.lib().pls_matmult(self.ptr, N.ptr(x), N.ptr(y)))
         return y
 
+    def matmult_single(self, x):
+        """y = A^ x: the outer operator with its stored values rounded to fp32 once, x and every sum
+        fp64 (pls_matmult_single; what -<prefix>pls_gmres_operator single multiplies with)."""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        y = np.empty_like(x)
+        N.check(N.lib().pls_matmult_single(self.ptr, N.ptr(x), N.ptr(y)))
+        return y
+
     def _guess_info(self, prefix):
         rx, t = C.c_int64(), C.c_double()
         N.check(N.lib().pls_get_ksp_guess_info(self.ptr, prefix.encode(), C.byref(rx), C.byref(t)))
@@ -203,12 +211,20 @@ class Handle:
     def matmult_device(self, d_x, d_y):
         N.check(N.lib().pls_matmult_device(self.ptr, d_x, d_y))
 
+    def matmult_single_device(self, d_x, d_y):
+        N.check(N.lib().pls_matmult_single_device(self.ptr, d_x, d_y))
+
     def rhs_device(self, seed, d_b):
         N.check(N.lib().pls_synthetic_rhs_device(self.ptr, int(seed), d_b))
 
     def bench_spmv(self, d_x, d_y, reps):
         s = C.c_double()
         N.check(N.lib().pls_bench_spmv(self.ptr, d_x, d_y, int(reps), C.byref(s)))
+        return s.value
+
+    def bench_spmv_single(self, d_x, d_y, reps):
+        s = C.c_double()
+        N.check(N.lib().pls_bench_spmv_single(self.ptr, d_x, d_y, int(reps), C.byref(s)))
         return s.value
 
     def bench_global_sum(self, count, reps):
@@ -220,6 +236,12 @@ class Handle:
         """(is SELL-64/D16, matrix bytes streamed per product of A)."""
         d, b = C.c_int32(), C.c_int64()
         N.check(N.lib().pls_spmv_layout(self.ptr, C.byref(d), C.byref(b)))
+        return bool(d.value), b.value
+
+    def spmv_layout_single(self):
+        """(can A's layout carry the fp32 value stream, matrix bytes streamed per low product of A)."""
+        d, b = C.c_int32(), C.c_int64()
+        N.check(N.lib().pls_spmv_layout_single(self.ptr, C.byref(d), C.byref(b)))
         return bool(d.value), b.value
 
     # -------------------------------------------------------------- queries --
@@ -263,6 +285,14 @@ class Handle:
         N.check(N.lib().pls_get_gmres_basis_stats(self.ptr, prefix.encode(), N.ptr(s)))
         return tuple(int(v) for v in s)
 
+    def gmres_operator_stats(self, prefix):
+        """(operator precision inside the Arnoldi step: 0 double, 1 single; bytes of the fp32 value
+        streams held; low-precision products; fp64 products) of the gmres / fgmres solver with this
+        options prefix (pls_get_gmres_operator_stats)."""
+        s = np.zeros(4, dtype=np.int64)
+        N.check(N.lib().pls_get_gmres_operator_stats(self.ptr, prefix.encode(), N.ptr(s)))
+        return tuple(int(v) for v in s)
+
     def ksp_guess_stats(self, prefix):
         """((type: 0 none, 1 fischer; columns stored now; size; guesses formed; updates skipped;
         resets), ||b - A x0|| / ||b|| of the most recent guessed solve -- NaN before the first) of
@@ -299,6 +329,13 @@ class Handle:
         s = np.zeros(3, dtype=np.int64)
         N.check(N.lib().pls_get_reuse_stats(self.ptr, N.ptr(s)))
         return tuple(int(v) for v in s)
+
+    def reuse_rows(self):
+        """uint8 mask, the caller's row order: 1 on the rows the reduced outer product starts from
+        the block PC's raw sums; all 0 while the coupling reuse is not eligible (pls_get_reuse_rows)."""
+        m = np.zeros(self.n, dtype=np.uint8)
+        N.check(N.lib().pls_get_reuse_rows(self.ptr, N.ptr(m)))
+        return m
 
     def reset_timings(self):
         N.check(N.lib().pls_reset_timings(self.ptr))
