@@ -17,6 +17,7 @@
 #include <hipcub/hipcub.hpp>
 
 #include <cstdio>
+#include <type_traits>
 
 namespace pls {
 
@@ -756,72 +757,128 @@ __global__ __launch_bounds__(TPB) void k_final(int nb, const double *partial, do
     if (threadIdx.x == 0) out[j] = sqrt_it ? sqrt(v) : v;
 }
 
-// mdot: blockIdx.x = chunk, blockIdx.y = group of MDOT_NJ vectors
-// CGS dot block h_j = V_j . w, j in [0, k): blocks of MDOT_NJ columns per
-// grid row, 16-B loads (pairs of rows; chunks start on even rows, V columns
-// are 512-B aligned), one partial per (column, block) -> k_final in fixed order.
+// ----------------------------------------------------- Krylov basis kernels --
+// k_mdot / k_maxpy_norm / k_mgs_step / k_lincomb over a Krylov basis stored as T: double, or
+// float (compressed-basis GMRES, pls_gmres_basis single: the columns are read as floats and
+// promoted, w and every sum stay fp64).  One data path: 16-B loads of a column -- R rows per
+// lane, 2 of a double basis and 4 of a float one, with R / 2 loads for the matching rows of
+// w -- chunks that start on multiples of R rows (columns are 512-B aligned), two trips of
+// loads issued ahead of their FMAs, each lane summing its rows in ascending order (first trip
+// before second), the n mod R tail rows of the last chunk in thread 0 after its vector rows.
 typedef double cgs_d2 __attribute__((ext_vector_type(2)));
-static constexpr int MDOT_NJ = 16;
-__device__ __forceinline__ void chunk_even(int64_t n, int nb, int b, int64_t &s, int64_t &e) {
+typedef float cb_f4 __attribute__((ext_vector_type(4)));
+template <class T>
+struct basis_load;  // one 16-B load of a basis column
+template <>
+struct basis_load<double> {
+    static constexpr int R = 2;
+    typedef cgs_d2 vec;
+};
+template <>
+struct basis_load<float> {
+    static constexpr int R = 4;
+    typedef cb_f4 vec;
+};
+template <int R>
+struct w_rows {  // the R rows of w (or of a sum) beside one basis load
+    cgs_d2 p[R / 2];
+};
+template <int N>
+__device__ __forceinline__ void chunk_rows(int64_t n, int nb, int b, int64_t &s, int64_t &e) {
     int64_t c = (n + nb - 1) / nb;
-    c = (c + 1) & ~(int64_t)1;
+    c = (c + N - 1) & ~(int64_t)(N - 1);
     s = (int64_t)b * c;
     e = s + c;
     if (e > n) e = n;
     if (s > n) s = n;
 }
-__global__ __launch_bounds__(TPB) void k_mdot(int64_t n, int k, const double *__restrict__ V, int64_t ldv,
+__device__ __forceinline__ cgs_d2 cb_ld2(const double *p) { return *reinterpret_cast<const cgs_d2 *>(p); }
+template <class T>
+__device__ __forceinline__ typename basis_load<T>::vec basis_ld(const T *p) {
+    return *reinterpret_cast<const typename basis_load<T>::vec *>(p);
+}
+template <int R>
+__device__ __forceinline__ w_rows<R> w_ld(const double *p) {
+    w_rows<R> t;
+#pragma unroll
+    for (int q = 0; q < R / 2; ++q) t.p[q] = cb_ld2(p + 2 * q);
+    return t;
+}
+template <int R>
+__device__ __forceinline__ void w_st(double *p, const w_rows<R> &t) {
+#pragma unroll
+    for (int q = 0; q < R / 2; ++q) *reinterpret_cast<cgs_d2 *>(p + 2 * q) = t.p[q];
+}
+// a += v . w over the R rows, ascending
+template <class VEC, int R>
+__device__ __forceinline__ void rows_dot(double &a, const VEC v, const w_rows<R> &w) {
+#pragma unroll
+    for (int r = 0; r < R; ++r) a += (double)v[r] * w.p[r >> 1][r & 1];
+}
+// t -= h v over the R rows
+template <class VEC, int R>
+__device__ __forceinline__ void rows_sub(w_rows<R> &t, double h, const VEC v) {
+#pragma unroll
+    for (int r = 0; r < R; ++r) t.p[r >> 1][r & 1] -= h * (double)v[r];
+}
+// a += t . t
+template <int R>
+__device__ __forceinline__ void rows_sq(double &a, const w_rows<R> &t) {
+#pragma unroll
+    for (int r = 0; r < R; ++r) a += t.p[r >> 1][r & 1] * t.p[r >> 1][r & 1];
+}
+
+// mdot: blockIdx.x = chunk, blockIdx.y = group of MDOT_NJ vectors
+// CGS dot block h_j = V_j . w, j in [0, k): blocks of MDOT_NJ columns per
+// grid row, one partial per (column, block) -> k_final in fixed order.
+static constexpr int MDOT_NJ = 16;
+template <class T>
+__global__ __launch_bounds__(TPB) void k_mdot(int64_t n, int k, const T *__restrict__ V, int64_t ldv,
                                               const double *__restrict__ w, double *partial) {
+    constexpr int R = basis_load<T>::R;
     __shared__ double lds[TPB / 64];
     const int nb = gridDim.x;
     int64_t s, e;
-    chunk_even(n, nb, blockIdx.x, s, e);
+    chunk_rows<R>(n, nb, blockIdx.x, s, e);
     const int j0 = blockIdx.y * MDOT_NJ;
     const int nj = (k - j0) < MDOT_NJ ? (k - j0) : MDOT_NJ;
     double a[MDOT_NJ];
 #pragma unroll
     for (int u = 0; u < MDOT_NJ; ++u) a[u] = 0.0;
-    const double *v0 = V + (int64_t)j0 * ldv;
-    int64_t i = s + 2 * threadIdx.x;
-    // two row pairs per trip, all their loads issued before the FMAs (twice the
-    // bytes in flight; the same per-thread summation order as one pair a trip)
-    for (; i + 2 * TPB + 1 < e; i += 4 * TPB) {
-        const cgs_d2 wa = *reinterpret_cast<const cgs_d2 *>(w + i);
-        const cgs_d2 wb = *reinterpret_cast<const cgs_d2 *>(w + i + 2 * TPB);
-        cgs_d2 va[MDOT_NJ], vb[MDOT_NJ];
+    const T *v0 = V + (int64_t)j0 * ldv;
+    int64_t i = s + R * threadIdx.x;
+    // two loads per column and trip, all of them issued before the FMAs (twice the
+    // bytes in flight; the same per-thread summation order as one load a trip)
+    for (; i + R * TPB + R - 1 < e; i += 2 * R * TPB) {
+        const w_rows<R> wa = w_ld<R>(w + i), wb = w_ld<R>(w + i + R * TPB);
+        typename basis_load<T>::vec va[MDOT_NJ], vb[MDOT_NJ];
 #pragma unroll
         for (int u = 0; u < MDOT_NJ; ++u) {
             if (u < nj) {
-                va[u] = *reinterpret_cast<const cgs_d2 *>(v0 + (int64_t)u * ldv + i);
-                vb[u] = *reinterpret_cast<const cgs_d2 *>(v0 + (int64_t)u * ldv + i + 2 * TPB);
+                va[u] = basis_ld(v0 + (int64_t)u * ldv + i);
+                vb[u] = basis_ld(v0 + (int64_t)u * ldv + i + R * TPB);
             }
         }
 #pragma unroll
         for (int u = 0; u < MDOT_NJ; ++u) {
             if (u < nj) {
-                a[u] += va[u].x * wa.x;
-                a[u] += va[u].y * wa.y;
-                a[u] += vb[u].x * wb.x;
-                a[u] += vb[u].y * wb.y;
+                rows_dot(a[u], va[u], wa);
+                rows_dot(a[u], vb[u], wb);
             }
         }
     }
-    for (; i + 1 < e; i += 2 * TPB) {
-        const cgs_d2 wi = *reinterpret_cast<const cgs_d2 *>(w + i);
-#pragma unroll
-        for (int u = 0; u < MDOT_NJ; ++u) {
-            if (u < nj) {
-                const cgs_d2 v = *reinterpret_cast<const cgs_d2 *>(v0 + (int64_t)u * ldv + i);
-                a[u] += v.x * wi.x;
-                a[u] += v.y * wi.y;
-            }
-        }
-    }
-    if (((e - s) & 1) && threadIdx.x == 0) {
-        const int64_t i = e - 1;
+    for (; i + R - 1 < e; i += R * TPB) {
+        const w_rows<R> wi = w_ld<R>(w + i);
 #pragma unroll
         for (int u = 0; u < MDOT_NJ; ++u)
-            if (u < nj) a[u] += v0[(int64_t)u * ldv + i] * w[i];
+            if (u < nj) rows_dot(a[u], basis_ld(v0 + (int64_t)u * ldv + i), wi);
+    }
+    if (threadIdx.x == 0) {
+        for (int64_t l = e - ((e - s) & (R - 1)); l < e; ++l) {
+#pragma unroll
+            for (int u = 0; u < MDOT_NJ; ++u)
+                if (u < nj) a[u] += (double)v0[(int64_t)u * ldv + l] * w[l];
+        }
     }
 #pragma unroll
     for (int u = 0; u < MDOT_NJ; ++u) {
@@ -832,13 +889,22 @@ __global__ __launch_bounds__(TPB) void k_mdot(int64_t n, int k, const double *__
     }
 }
 
-void launch_mdot(int64_t n, int k, const double *const *, const double *V, int64_t ldv, const double *w,
-                 double *partial, double *out, hipStream_t st) {
+template <class T>
+static void mdot(int64_t n, int k, const T *V, int64_t ldv, const double *w, double *partial, double *out,
+                 hipStream_t st) {
     if (k <= 0) return;
     const int nb = reduce_blocks(n);
     dim3 grid(nb, (k + MDOT_NJ - 1) / MDOT_NJ);
-    k_mdot<<<grid, TPB, 0, st>>>(n, k, V, ldv, w, partial);
+    k_mdot<T><<<grid, TPB, 0, st>>>(n, k, V, ldv, w, partial);
     k_final<<<k, TPB, 0, st>>>(nb, partial, out, 0);
+}
+void launch_mdot(int64_t n, int k, const double *V, int64_t ldv, const double *w, double *partial, double *out,
+                 hipStream_t st) {
+    mdot(n, k, V, ldv, w, partial, out, st);
+}
+void launch_mdot(int64_t n, int k, const float *V, int64_t ldv, const double *w, double *partial, double *out,
+                 hipStream_t st) {
+    mdot(n, k, V, ldv, w, partial, out, st);
 }
 
 __global__ __launch_bounds__(TPB) void k_dot(int64_t n, const double *__restrict__ x, const double *__restrict__ y,
@@ -1082,87 +1148,73 @@ void launch_final(int64_t n, int rows, const double *partial, double *out, hipSt
 }
 
 // w -= sum_j h[j] V[:, j] (j ascending, as VecMAXPY); partial ||w||^2.
-// Pairs of rows per thread (16-B loads), eight basis columns loaded ahead of
-// their FMAs so every lane keeps 8-9 loads in flight.
-__global__ __launch_bounds__(TPB) void k_maxpy_norm(int64_t n, int k, const double *__restrict__ V, int64_t ldv,
+// Eight basis columns loaded ahead of their FMAs so every lane keeps 8-9 loads in flight.
+template <class T>
+__global__ __launch_bounds__(TPB) void k_maxpy_norm(int64_t n, int k, const T *__restrict__ V, int64_t ldv,
                                                     const double *__restrict__ h, double *__restrict__ w,
                                                     double *partial) {
+    constexpr int R = basis_load<T>::R;
+    typedef typename basis_load<T>::vec vec;
     __shared__ double lds[TPB / 64];
     __shared__ double hs[512];
     for (int j = threadIdx.x; j < k && j < 512; j += TPB) hs[j] = h[j];
     __syncthreads();
     int64_t s, e;
-    chunk_even(n, gridDim.x, blockIdx.x, s, e);
+    chunk_rows<R>(n, gridDim.x, blockIdx.x, s, e);
     double a = 0.0;
-    int64_t i = s + 2 * threadIdx.x;
-    // two row pairs per trip (loads of both ahead of their FMAs; the norm sums
-    // the pairs in the same order as one pair a trip)
-    for (; i + 2 * TPB + 1 < e; i += 4 * TPB) {
-        cgs_d2 ta = *reinterpret_cast<const cgs_d2 *>(w + i);
-        cgs_d2 tb = *reinterpret_cast<const cgs_d2 *>(w + i + 2 * TPB);
+    int64_t i = s + R * threadIdx.x;
+    // two loads per column and trip (both ahead of their FMAs; the norm sums
+    // the rows in the same order as one load a trip)
+    for (; i + R * TPB + R - 1 < e; i += 2 * R * TPB) {
+        w_rows<R> ta = w_ld<R>(w + i), tb = w_ld<R>(w + i + R * TPB);
         int j = 0;
         for (; j + 8 <= k; j += 8) {
-            cgs_d2 va[8], vb[8];
+            vec va[8], vb[8];
 #pragma unroll
             for (int u = 0; u < 8; ++u) {
-                va[u] = *reinterpret_cast<const cgs_d2 *>(V + (int64_t)(j + u) * ldv + i);
-                vb[u] = *reinterpret_cast<const cgs_d2 *>(V + (int64_t)(j + u) * ldv + i + 2 * TPB);
+                va[u] = basis_ld(V + (int64_t)(j + u) * ldv + i);
+                vb[u] = basis_ld(V + (int64_t)(j + u) * ldv + i + R * TPB);
             }
 #pragma unroll
             for (int u = 0; u < 8; ++u) {
                 const double hj = (j + u) < 512 ? hs[j + u] : h[j + u];
-                ta.x -= hj * va[u].x;
-                ta.y -= hj * va[u].y;
-                tb.x -= hj * vb[u].x;
-                tb.y -= hj * vb[u].y;
+                rows_sub(ta, hj, va[u]);
+                rows_sub(tb, hj, vb[u]);
             }
         }
         for (; j < k; ++j) {
-            const cgs_d2 va = *reinterpret_cast<const cgs_d2 *>(V + (int64_t)j * ldv + i);
-            const cgs_d2 vb = *reinterpret_cast<const cgs_d2 *>(V + (int64_t)j * ldv + i + 2 * TPB);
+            const vec va = basis_ld(V + (int64_t)j * ldv + i);
+            const vec vb = basis_ld(V + (int64_t)j * ldv + i + R * TPB);
             const double hj = j < 512 ? hs[j] : h[j];
-            ta.x -= hj * va.x;
-            ta.y -= hj * va.y;
-            tb.x -= hj * vb.x;
-            tb.y -= hj * vb.y;
+            rows_sub(ta, hj, va);
+            rows_sub(tb, hj, vb);
         }
-        *reinterpret_cast<cgs_d2 *>(w + i) = ta;
-        *reinterpret_cast<cgs_d2 *>(w + i + 2 * TPB) = tb;
-        a += ta.x * ta.x;
-        a += ta.y * ta.y;
-        a += tb.x * tb.x;
-        a += tb.y * tb.y;
+        w_st<R>(w + i, ta);
+        w_st<R>(w + i + R * TPB, tb);
+        rows_sq(a, ta);
+        rows_sq(a, tb);
     }
-    for (; i + 1 < e; i += 2 * TPB) {
-        cgs_d2 t = *reinterpret_cast<const cgs_d2 *>(w + i);
+    for (; i + R - 1 < e; i += R * TPB) {
+        w_rows<R> t = w_ld<R>(w + i);
         int j = 0;
         for (; j + 8 <= k; j += 8) {
-            cgs_d2 v[8];
+            vec v[8];
 #pragma unroll
-            for (int u = 0; u < 8; ++u) v[u] = *reinterpret_cast<const cgs_d2 *>(V + (int64_t)(j + u) * ldv + i);
+            for (int u = 0; u < 8; ++u) v[u] = basis_ld(V + (int64_t)(j + u) * ldv + i);
 #pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const double hj = (j + u) < 512 ? hs[j + u] : h[j + u];
-                t.x -= hj * v[u].x;
-                t.y -= hj * v[u].y;
-            }
+            for (int u = 0; u < 8; ++u) rows_sub(t, (j + u) < 512 ? hs[j + u] : h[j + u], v[u]);
         }
-        for (; j < k; ++j) {
-            const cgs_d2 v = *reinterpret_cast<const cgs_d2 *>(V + (int64_t)j * ldv + i);
-            const double hj = j < 512 ? hs[j] : h[j];
-            t.x -= hj * v.x;
-            t.y -= hj * v.y;
-        }
-        *reinterpret_cast<cgs_d2 *>(w + i) = t;
-        a += t.x * t.x;
-        a += t.y * t.y;
+        for (; j < k; ++j) rows_sub(t, j < 512 ? hs[j] : h[j], basis_ld(V + (int64_t)j * ldv + i));
+        w_st<R>(w + i, t);
+        rows_sq(a, t);
     }
-    if (((e - s) & 1) && threadIdx.x == 0) {
-        const int64_t i = e - 1;
-        double t = w[i];
-        for (int j = 0; j < k; ++j) t -= (j < 512 ? hs[j] : h[j]) * V[(int64_t)j * ldv + i];
-        w[i] = t;
-        a += t * t;
+    if (threadIdx.x == 0) {
+        for (int64_t l = e - ((e - s) & (R - 1)); l < e; ++l) {
+            double t = w[l];
+            for (int j = 0; j < k; ++j) t -= (j < 512 ? hs[j] : h[j]) * (double)V[(int64_t)j * ldv + l];
+            w[l] = t;
+            a += t * t;
+        }
     }
     if (partial) {
         a = block_sum(a, lds);
@@ -1170,114 +1222,119 @@ __global__ __launch_bounds__(TPB) void k_maxpy_norm(int64_t n, int k, const doub
     }
 }
 
-void launch_maxpy_norm(int64_t n, int k, const double *V, int64_t ldv, const double *h_dev, double,
-                       double *w, double *partial, double *out, hipStream_t st) {
+template <class T>
+static void maxpy_norm(int64_t n, int k, const T *V, int64_t ldv, const double *h_dev, double *w, double *partial,
+                       double *out, hipStream_t st) {
     const int nb = reduce_blocks(n);
-    k_maxpy_norm<<<nb, TPB, 0, st>>>(n, k, V, ldv, h_dev, w, out ? partial : nullptr);
+    k_maxpy_norm<T><<<nb, TPB, 0, st>>>(n, k, V, ldv, h_dev, w, out ? partial : nullptr);
     if (out) k_final<<<1, TPB, 0, st>>>(nb, partial, out, 0);  // ||w||^2 (rank-local)
+}
+void launch_maxpy_norm(int64_t n, int k, const double *V, int64_t ldv, const double *h_dev, double *w,
+                       double *partial, double *out, hipStream_t st) {
+    maxpy_norm(n, k, V, ldv, h_dev, w, partial, out, st);
+}
+void launch_maxpy_norm(int64_t n, int k, const float *V, int64_t ldv, const double *h_dev, double *w, double *partial,
+                       double *out, hipStream_t st) {
+    maxpy_norm(n, k, V, ldv, h_dev, w, partial, out, st);
 }
 
 // One step of modified Gram-Schmidt (KSPGMRESModifiedGramSchmidtOrthogonalization):
 // w -= (*hprev) vprev first (vprev != null), then this block's part of (w, vj)
-// over the updated rows -- (w, w) when vj is null.  k_mdot's data path: chunks
-// on even rows, 16-B loads of row pairs, two pairs per trip with their loads
-// ahead of the FMAs, the odd tail row in thread 0.  Every row is read and
-// written by one thread of one block, so no block depends on another's rows.
-// With a ticket the last block to arrive sums the parts (ticket_totals, in
-// k_final's order) into *out, where the next step's launch reads its
-// coefficient; without one they go to partial[block] for k_final.
-__global__ __launch_bounds__(TPB) void k_mgs_step(int64_t n, const double *__restrict__ vprev,
-                                                  const double *__restrict__ hprev, const double *__restrict__ vj,
+// over the updated rows -- (w, w) when vj is null.  k_mdot's data path.  Every
+// row is read and written by one thread of one block, so no block depends on
+// another's rows.  Without a ticket the parts go to partial[block] for k_final.
+// With one (double basis only) the last block to arrive sums them
+// (ticket_totals, in k_final's order) into *out, where the next step's launch
+// reads its coefficient.
+template <class T>
+__global__ __launch_bounds__(TPB) void k_mgs_step(int64_t n, const T *__restrict__ vprev,
+                                                  const double *__restrict__ hprev, const T *__restrict__ vj,
                                                   double *w, double *partial, double *out, unsigned *ticket) {
+    constexpr int R = basis_load<T>::R;
+    typedef typename basis_load<T>::vec vec;
     __shared__ double lds[TPB / 64];
     int64_t s, e;
-    chunk_even(n, gridDim.x, blockIdx.x, s, e);
+    chunk_rows<R>(n, gridDim.x, blockIdx.x, s, e);
     const double hp = vprev ? *hprev : 0.0;
     double a[1] = {0.0};
-    int64_t i = s + 2 * threadIdx.x;
-    for (; i + 2 * TPB + 1 < e; i += 4 * TPB) {
-        cgs_d2 ta = *reinterpret_cast<const cgs_d2 *>(w + i);
-        cgs_d2 tb = *reinterpret_cast<const cgs_d2 *>(w + i + 2 * TPB);
-        cgs_d2 pa = {0.0, 0.0}, pb = {0.0, 0.0}, va = {0.0, 0.0}, vb = {0.0, 0.0};
+    // the R rows at i: the update by vprev, then their part of (w, vj) or (w, w)
+    auto rows = [&](int64_t i, w_rows<R> t, const vec p, const vec v) {
         if (vprev) {
-            pa = *reinterpret_cast<const cgs_d2 *>(vprev + i);
-            pb = *reinterpret_cast<const cgs_d2 *>(vprev + i + 2 * TPB);
+            rows_sub(t, hp, p);
+            w_st<R>(w + i, t);
+        }
+        if (vj) rows_dot(a[0], v, t);
+        else rows_sq(a[0], t);
+    };
+    const vec zero = {};
+    int64_t i = s + R * threadIdx.x;
+    for (; i + R * TPB + R - 1 < e; i += 2 * R * TPB) {
+        const w_rows<R> ta = w_ld<R>(w + i), tb = w_ld<R>(w + i + R * TPB);
+        vec pa = zero, pb = zero, va = zero, vb = zero;
+        if (vprev) {
+            pa = basis_ld(vprev + i);
+            pb = basis_ld(vprev + i + R * TPB);
         }
         if (vj) {
-            va = *reinterpret_cast<const cgs_d2 *>(vj + i);
-            vb = *reinterpret_cast<const cgs_d2 *>(vj + i + 2 * TPB);
+            va = basis_ld(vj + i);
+            vb = basis_ld(vj + i + R * TPB);
         }
-        if (vprev) {
-            ta.x -= hp * pa.x;
-            ta.y -= hp * pa.y;
-            tb.x -= hp * pb.x;
-            tb.y -= hp * pb.y;
-            *reinterpret_cast<cgs_d2 *>(w + i) = ta;
-            *reinterpret_cast<cgs_d2 *>(w + i + 2 * TPB) = tb;
-        }
-        if (!vj) {
-            va = ta;
-            vb = tb;
-        }
-        a[0] += va.x * ta.x;
-        a[0] += va.y * ta.y;
-        a[0] += vb.x * tb.x;
-        a[0] += vb.y * tb.y;
+        rows(i, ta, pa, va);
+        rows(i + R * TPB, tb, pb, vb);
     }
-    for (; i + 1 < e; i += 2 * TPB) {
-        cgs_d2 t = *reinterpret_cast<const cgs_d2 *>(w + i);
-        cgs_d2 v = {0.0, 0.0};
-        if (vj) v = *reinterpret_cast<const cgs_d2 *>(vj + i);
-        if (vprev) {
-            const cgs_d2 p = *reinterpret_cast<const cgs_d2 *>(vprev + i);
-            t.x -= hp * p.x;
-            t.y -= hp * p.y;
-            *reinterpret_cast<cgs_d2 *>(w + i) = t;
+    for (; i + R - 1 < e; i += R * TPB)
+        rows(i, w_ld<R>(w + i), vprev ? basis_ld(vprev + i) : zero, vj ? basis_ld(vj + i) : zero);
+    if (threadIdx.x == 0) {
+        for (int64_t l = e - ((e - s) & (R - 1)); l < e; ++l) {
+            double t = w[l];
+            if (vprev) {
+                t -= hp * (double)vprev[l];
+                w[l] = t;
+            }
+            a[0] += (vj ? (double)vj[l] : t) * t;
         }
-        if (!vj) v = t;
-        a[0] += v.x * t.x;
-        a[0] += v.y * t.y;
-    }
-    if (((e - s) & 1) && threadIdx.x == 0) {
-        const int64_t l = e - 1;
-        double t = w[l];
-        if (vprev) {
-            t -= hp * vprev[l];
-            w[l] = t;
-        }
-        a[0] += (vj ? vj[l] : t) * t;
     }
     a[0] = block_sum(a[0], lds);
-    if (!ticket) {
-        if (threadIdx.x == 0) partial[blockIdx.x] = a[0];
-        return;
+    if constexpr (std::is_same<T, double>::value) {
+        if (ticket) {
+            double tot[1];
+            if (!ticket_totals<1>(a, partial, lds, ticket, tot)) return;
+            if (threadIdx.x == 0) {
+                *out = tot[0];
+                ticket_reset(ticket);
+            }
+            return;
+        }
     }
-    double tot[1];
-    if (!ticket_totals<1>(a, partial, lds, ticket, tot)) return;
-    if (threadIdx.x == 0) {
-        *out = tot[0];
-        ticket_reset(ticket);
-    }
+    if (threadIdx.x == 0) partial[blockIdx.x] = a[0];
 }
 void launch_mgs_step(int64_t n, const double *vprev, const double *hprev, const double *vj, double *w, double *partial,
                      double *out, unsigned *ticket, hipStream_t st) {
-    k_mgs_step<<<reduce_blocks(n), TPB, 0, st>>>(n, vprev, hprev, vj, w, partial, out, ticket);
+    k_mgs_step<double><<<reduce_blocks(n), TPB, 0, st>>>(n, vprev, hprev, vj, w, partial, out, ticket);
+}
+void launch_mgs_step(int64_t n, const float *vprev, const double *hprev, const float *vj, double *w, double *partial,
+                     double *out, unsigned *ticket, hipStream_t st) {
+    k_mgs_step<float><<<reduce_blocks(n), TPB, 0, st>>>(n, vprev, hprev, vj, w, partial, out, ticket);
 }
 
-__global__ __launch_bounds__(TPB) void k_lincomb(int64_t n, int k, const double *__restrict__ V, int64_t ldv,
+template <class T>
+__global__ __launch_bounds__(TPB) void k_lincomb(int64_t n, int k, const T *__restrict__ V, int64_t ldv,
                                                  const double *__restrict__ c, double *__restrict__ y) {
     __shared__ double cs[512];
     for (int j = threadIdx.x; j < k && j < 512; j += TPB) cs[j] = c[j];
     __syncthreads();
     for (int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x; i < n; i += (int64_t)gridDim.x * TPB) {
         double t = 0.0;
-        for (int j = 0; j < k; ++j) t += (j < 512 ? cs[j] : c[j]) * V[(int64_t)j * ldv + i];
+        for (int j = 0; j < k; ++j) t += (j < 512 ? cs[j] : c[j]) * (double)V[(int64_t)j * ldv + i];
         y[i] = t;
     }
 }
 void launch_lincomb(int64_t n, int k, const double *V, int64_t ldv, const double *c_dev, double *y,
                     hipStream_t st) {
-    if (n > 0) k_lincomb<<<stream_grid(n), TPB, 0, st>>>(n, k, V, ldv, c_dev, y);
+    if (n > 0) k_lincomb<double><<<stream_grid(n), TPB, 0, st>>>(n, k, V, ldv, c_dev, y);
+}
+void launch_lincomb(int64_t n, int k, const float *V, int64_t ldv, const double *c_dev, double *y, hipStream_t st) {
+    if (n > 0) k_lincomb<float><<<stream_grid(n), TPB, 0, st>>>(n, k, V, ldv, c_dev, y);
 }
 
 // ------------------------------------------- Fischer guess (KSPGuess, model 2) --
@@ -1301,7 +1358,7 @@ __global__ __launch_bounds__(TPB) void k_guess_update(int64_t n, int m, const do
     for (int j = threadIdx.x; j < m && j < GUESS_MAX; j += TPB) as[j] = alpha[j];
     __syncthreads();
     int64_t s, e;
-    chunk_even(n, gridDim.x, blockIdx.x, s, e);
+    chunk_rows<2>(n, gridDim.x, blockIdx.x, s, e);
     double a = 0.0;
     int64_t i = s + 2 * threadIdx.x;
     for (; i + 2 * TPB + 1 < e; i += 4 * TPB) {
@@ -1441,270 +1498,6 @@ void launch_scale2(int64_t n, double a, double *u, double *v, hipStream_t st) {
 }
 
 // ------------------------------------------ compressed-basis GMRES (fp32 V) --
-// The counterparts of k_mdot / k_maxpy_norm / k_mgs_step / k_lincomb for a
-// Krylov basis stored in fp32 (pls_gmres_basis single): the columns are read as
-// floats and promoted, w and every sum stay fp64.  The data path is the double
-// kernels': 16-B loads -- four rows of a column per lane, two loads for the
-// matching rows of w -- chunks that start on multiples of 4 rows (columns are
-// 512-B aligned: ldv a multiple of 128 floats), two trips of loads issued ahead
-// of their FMAs, each lane summing its rows in ascending order, one partial per
-// (column, block) for k_final.  The n mod 4 tail rows of the last chunk are
-// thread 0's, after its vector rows, as the odd row is in the double kernels.
-typedef float cb_f4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void chunk_quad(int64_t n, int nb, int b, int64_t &s, int64_t &e) {
-    int64_t c = (n + nb - 1) / nb;
-    c = (c + 3) & ~(int64_t)3;
-    s = (int64_t)b * c;
-    e = s + c;
-    if (e > n) e = n;
-    if (s > n) s = n;
-}
-__device__ __forceinline__ cb_f4 cb_ld(const float *p) { return *reinterpret_cast<const cb_f4 *>(p); }
-__device__ __forceinline__ cgs_d2 cb_ld2(const double *p) { return *reinterpret_cast<const cgs_d2 *>(p); }
-// a += v . w over four rows, ascending
-__device__ __forceinline__ void cb_dot4(double &a, const cb_f4 v, const cgs_d2 w0, const cgs_d2 w1) {
-    a += (double)v.x * w0.x;
-    a += (double)v.y * w0.y;
-    a += (double)v.z * w1.x;
-    a += (double)v.w * w1.y;
-}
-// t -= h v over four rows
-__device__ __forceinline__ void cb_sub4(cgs_d2 &t0, cgs_d2 &t1, double h, const cb_f4 v) {
-    t0.x -= h * (double)v.x;
-    t0.y -= h * (double)v.y;
-    t1.x -= h * (double)v.z;
-    t1.y -= h * (double)v.w;
-}
-
-__global__ __launch_bounds__(TPB) void k_mdot_f32(int64_t n, int k, const float *__restrict__ V, int64_t ldv,
-                                                  const double *__restrict__ w, double *partial) {
-    __shared__ double lds[TPB / 64];
-    const int nb = gridDim.x;
-    int64_t s, e;
-    chunk_quad(n, nb, blockIdx.x, s, e);
-    const int j0 = blockIdx.y * MDOT_NJ;
-    const int nj = (k - j0) < MDOT_NJ ? (k - j0) : MDOT_NJ;
-    double a[MDOT_NJ];
-#pragma unroll
-    for (int u = 0; u < MDOT_NJ; ++u) a[u] = 0.0;
-    const float *v0 = V + (int64_t)j0 * ldv;
-    int64_t i = s + 4 * threadIdx.x;
-    for (; i + 4 * TPB + 3 < e; i += 8 * TPB) {
-        const cgs_d2 wa0 = cb_ld2(w + i), wa1 = cb_ld2(w + i + 2);
-        const cgs_d2 wb0 = cb_ld2(w + i + 4 * TPB), wb1 = cb_ld2(w + i + 4 * TPB + 2);
-        cb_f4 va[MDOT_NJ], vb[MDOT_NJ];
-#pragma unroll
-        for (int u = 0; u < MDOT_NJ; ++u) {
-            if (u < nj) {
-                va[u] = cb_ld(v0 + (int64_t)u * ldv + i);
-                vb[u] = cb_ld(v0 + (int64_t)u * ldv + i + 4 * TPB);
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < MDOT_NJ; ++u) {
-            if (u < nj) {
-                cb_dot4(a[u], va[u], wa0, wa1);
-                cb_dot4(a[u], vb[u], wb0, wb1);
-            }
-        }
-    }
-    for (; i + 3 < e; i += 4 * TPB) {
-        const cgs_d2 w0 = cb_ld2(w + i), w1 = cb_ld2(w + i + 2);
-#pragma unroll
-        for (int u = 0; u < MDOT_NJ; ++u)
-            if (u < nj) cb_dot4(a[u], cb_ld(v0 + (int64_t)u * ldv + i), w0, w1);
-    }
-    if (threadIdx.x == 0) {
-        for (int64_t l = e - ((e - s) & 3); l < e; ++l) {
-#pragma unroll
-            for (int u = 0; u < MDOT_NJ; ++u)
-                if (u < nj) a[u] += (double)v0[(int64_t)u * ldv + l] * w[l];
-        }
-    }
-#pragma unroll
-    for (int u = 0; u < MDOT_NJ; ++u) {
-        if (u < nj) {
-            const double r = block_sum(a[u], lds);
-            if (threadIdx.x == 0) partial[(int64_t)(j0 + u) * nb + blockIdx.x] = r;
-        }
-    }
-}
-void launch_mdot_f32(int64_t n, int k, const float *V, int64_t ldv, const double *w, double *partial, double *out,
-                     hipStream_t st) {
-    if (k <= 0) return;
-    const int nb = reduce_blocks(n);
-    dim3 grid(nb, (k + MDOT_NJ - 1) / MDOT_NJ);
-    k_mdot_f32<<<grid, TPB, 0, st>>>(n, k, V, ldv, w, partial);
-    k_final<<<k, TPB, 0, st>>>(nb, partial, out, 0);
-}
-
-__global__ __launch_bounds__(TPB) void k_maxpy_norm_f32(int64_t n, int k, const float *__restrict__ V, int64_t ldv,
-                                                        const double *__restrict__ h, double *__restrict__ w,
-                                                        double *partial) {
-    __shared__ double lds[TPB / 64];
-    __shared__ double hs[512];
-    for (int j = threadIdx.x; j < k && j < 512; j += TPB) hs[j] = h[j];
-    __syncthreads();
-    int64_t s, e;
-    chunk_quad(n, gridDim.x, blockIdx.x, s, e);
-    double a = 0.0;
-    int64_t i = s + 4 * threadIdx.x;
-    for (; i + 4 * TPB + 3 < e; i += 8 * TPB) {
-        cgs_d2 ta0 = cb_ld2(w + i), ta1 = cb_ld2(w + i + 2);
-        cgs_d2 tb0 = cb_ld2(w + i + 4 * TPB), tb1 = cb_ld2(w + i + 4 * TPB + 2);
-        int j = 0;
-        for (; j + 8 <= k; j += 8) {
-            cb_f4 va[8], vb[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                va[u] = cb_ld(V + (int64_t)(j + u) * ldv + i);
-                vb[u] = cb_ld(V + (int64_t)(j + u) * ldv + i + 4 * TPB);
-            }
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const double hj = (j + u) < 512 ? hs[j + u] : h[j + u];
-                cb_sub4(ta0, ta1, hj, va[u]);
-                cb_sub4(tb0, tb1, hj, vb[u]);
-            }
-        }
-        for (; j < k; ++j) {
-            const cb_f4 va = cb_ld(V + (int64_t)j * ldv + i);
-            const cb_f4 vb = cb_ld(V + (int64_t)j * ldv + i + 4 * TPB);
-            const double hj = j < 512 ? hs[j] : h[j];
-            cb_sub4(ta0, ta1, hj, va);
-            cb_sub4(tb0, tb1, hj, vb);
-        }
-        *reinterpret_cast<cgs_d2 *>(w + i) = ta0;
-        *reinterpret_cast<cgs_d2 *>(w + i + 2) = ta1;
-        *reinterpret_cast<cgs_d2 *>(w + i + 4 * TPB) = tb0;
-        *reinterpret_cast<cgs_d2 *>(w + i + 4 * TPB + 2) = tb1;
-        a += ta0.x * ta0.x;
-        a += ta0.y * ta0.y;
-        a += ta1.x * ta1.x;
-        a += ta1.y * ta1.y;
-        a += tb0.x * tb0.x;
-        a += tb0.y * tb0.y;
-        a += tb1.x * tb1.x;
-        a += tb1.y * tb1.y;
-    }
-    for (; i + 3 < e; i += 4 * TPB) {
-        cgs_d2 t0 = cb_ld2(w + i), t1 = cb_ld2(w + i + 2);
-        int j = 0;
-        for (; j + 8 <= k; j += 8) {
-            cb_f4 v[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) v[u] = cb_ld(V + (int64_t)(j + u) * ldv + i);
-#pragma unroll
-            for (int u = 0; u < 8; ++u) cb_sub4(t0, t1, (j + u) < 512 ? hs[j + u] : h[j + u], v[u]);
-        }
-        for (; j < k; ++j) cb_sub4(t0, t1, j < 512 ? hs[j] : h[j], cb_ld(V + (int64_t)j * ldv + i));
-        *reinterpret_cast<cgs_d2 *>(w + i) = t0;
-        *reinterpret_cast<cgs_d2 *>(w + i + 2) = t1;
-        a += t0.x * t0.x;
-        a += t0.y * t0.y;
-        a += t1.x * t1.x;
-        a += t1.y * t1.y;
-    }
-    if (threadIdx.x == 0) {
-        for (int64_t l = e - ((e - s) & 3); l < e; ++l) {
-            double t = w[l];
-            for (int j = 0; j < k; ++j) t -= (j < 512 ? hs[j] : h[j]) * (double)V[(int64_t)j * ldv + l];
-            w[l] = t;
-            a += t * t;
-        }
-    }
-    if (partial) {
-        a = block_sum(a, lds);
-        if (threadIdx.x == 0) partial[blockIdx.x] = a;
-    }
-}
-void launch_maxpy_norm_f32(int64_t n, int k, const float *V, int64_t ldv, const double *h_dev, double *w,
-                           double *partial, double *out, hipStream_t st) {
-    const int nb = reduce_blocks(n);
-    k_maxpy_norm_f32<<<nb, TPB, 0, st>>>(n, k, V, ldv, h_dev, w, out ? partial : nullptr);
-    if (out) k_final<<<1, TPB, 0, st>>>(nb, partial, out, 0);
-}
-
-// k_mgs_step over fp32 columns (no single-launch sums: k_final follows every step)
-__global__ __launch_bounds__(TPB) void k_mgs_step_f32(int64_t n, const float *__restrict__ vprev,
-                                                      const double *__restrict__ hprev, const float *__restrict__ vj,
-                                                      double *w, double *partial) {
-    __shared__ double lds[TPB / 64];
-    int64_t s, e;
-    chunk_quad(n, gridDim.x, blockIdx.x, s, e);
-    const double hp = vprev ? *hprev : 0.0;
-    double a = 0.0;
-    // four rows at i: the update by vprev, then their part of (w, vj) or (w, w)
-    auto quad = [&](int64_t i, cgs_d2 t0, cgs_d2 t1, const cb_f4 p, const cb_f4 v) {
-        if (vprev) {
-            cb_sub4(t0, t1, hp, p);
-            *reinterpret_cast<cgs_d2 *>(w + i) = t0;
-            *reinterpret_cast<cgs_d2 *>(w + i + 2) = t1;
-        }
-        if (vj) {
-            cb_dot4(a, v, t0, t1);
-        } else {
-            a += t0.x * t0.x;
-            a += t0.y * t0.y;
-            a += t1.x * t1.x;
-            a += t1.y * t1.y;
-        }
-    };
-    const cb_f4 zero = {0.f, 0.f, 0.f, 0.f};
-    int64_t i = s + 4 * threadIdx.x;
-    for (; i + 4 * TPB + 3 < e; i += 8 * TPB) {
-        const cgs_d2 ta0 = cb_ld2(w + i), ta1 = cb_ld2(w + i + 2);
-        const cgs_d2 tb0 = cb_ld2(w + i + 4 * TPB), tb1 = cb_ld2(w + i + 4 * TPB + 2);
-        cb_f4 pa = zero, pb = zero, va = zero, vb = zero;
-        if (vprev) {
-            pa = cb_ld(vprev + i);
-            pb = cb_ld(vprev + i + 4 * TPB);
-        }
-        if (vj) {
-            va = cb_ld(vj + i);
-            vb = cb_ld(vj + i + 4 * TPB);
-        }
-        quad(i, ta0, ta1, pa, va);
-        quad(i + 4 * TPB, tb0, tb1, pb, vb);
-    }
-    for (; i + 3 < e; i += 4 * TPB) {
-        const cgs_d2 t0 = cb_ld2(w + i), t1 = cb_ld2(w + i + 2);
-        quad(i, t0, t1, vprev ? cb_ld(vprev + i) : zero, vj ? cb_ld(vj + i) : zero);
-    }
-    if (threadIdx.x == 0) {
-        for (int64_t l = e - ((e - s) & 3); l < e; ++l) {
-            double t = w[l];
-            if (vprev) {
-                t -= hp * (double)vprev[l];
-                w[l] = t;
-            }
-            a += (vj ? (double)vj[l] : t) * t;
-        }
-    }
-    a = block_sum(a, lds);
-    if (threadIdx.x == 0) partial[blockIdx.x] = a;
-}
-void launch_mgs_step_f32(int64_t n, const float *vprev, const double *hprev, const float *vj, double *w,
-                         double *partial, hipStream_t st) {
-    k_mgs_step_f32<<<reduce_blocks(n), TPB, 0, st>>>(n, vprev, hprev, vj, w, partial);
-}
-
-__global__ __launch_bounds__(TPB) void k_lincomb_f32(int64_t n, int k, const float *__restrict__ V, int64_t ldv,
-                                                     const double *__restrict__ c, double *__restrict__ y) {
-    __shared__ double cs[512];
-    for (int j = threadIdx.x; j < k && j < 512; j += TPB) cs[j] = c[j];
-    __syncthreads();
-    for (int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x; i < n; i += (int64_t)gridDim.x * TPB) {
-        double t = 0.0;
-        for (int j = 0; j < k; ++j) t += (j < 512 ? cs[j] : c[j]) * (double)V[(int64_t)j * ldv + i];
-        y[i] = t;
-    }
-}
-void launch_lincomb_f32(int64_t n, int k, const float *V, int64_t ldv, const double *c_dev, double *y,
-                        hipStream_t st) {
-    if (n > 0) k_lincomb_f32<<<stream_grid(n), TPB, 0, st>>>(n, k, V, ldv, c_dev, y);
-}
-
 // The new basis vector: vf = fl32(a w) (round to nearest even) and vd = vf promoted, the
 // vector the next operator / PC application reads, in one pass over w.  Four rows per lane
 // (vf, vd and w 32-B aligned, n >= 0 rows; the n mod 4 tail rows one lane each).
@@ -2768,6 +2561,31 @@ __global__ __launch_bounds__(TPB) void k_first_col(int64_t nrows, const int64_t 
 typedef int32_t d16_i4 __attribute__((ext_vector_type(4)));
 typedef uint32_t d16_u4 __attribute__((ext_vector_type(4)));
 typedef double d16_d2 __attribute__((ext_vector_type(2)));
+typedef float d16_f4 __attribute__((ext_vector_type(4)));
+
+// The value stream of a D16 layout as k_d16_spmv reads it: one 16-B pack per lane and load,
+//   fp64  dv[base + (k / 2) * 128 + lane * 2 + k % 2]    four packs per 8-entry group
+//   fp32  dv32[base + (k / 4) * 256 + lane * 4 + k % 4]  two (the low operator, see below)
+// get(v, e): entry e of a pack as the fp64 factor of the product.  UNROLL_MAX: the deepest
+// unroll of the stream; AUX_STORE: whether the raw-sum store is instantiated for it.
+template <class V>
+struct d16_values;
+template <>
+struct d16_values<double> {
+    typedef d16_d2 pack;
+    static constexpr int PER = 2, UNROLL_MAX = 4;
+    static constexpr bool AUX_STORE = true;
+    static __device__ __forceinline__ double get(const pack v, int e) { return e ? v.y : v.x; }
+};
+template <>
+struct d16_values<float> {
+    typedef d16_f4 pack;
+    static constexpr int PER = 4, UNROLL_MAX = 8;
+    static constexpr bool AUX_STORE = false;  // the raw-sum store belongs to the fp64 launch
+    static __device__ __forceinline__ double get(const pack v, int e) {
+        return (double)(e == 0 ? v.x : e == 1 ? v.y : e == 2 ? v.z : v.w);
+    }
+};
 
 __constant__ int d16_xcd_map;  // set once by launch_d16_spmv (pls.d16_xcd)
 
@@ -2776,17 +2594,22 @@ __constant__ int d16_xcd_map;  // set once by launch_d16_spmv (pls.d16_xcd)
 // gives the bits of the unbroken one):
 //   D16_AUX_STORE  aux[row] = acc, the raw row sum before alpha / beta
 //   D16_AUX_INIT   acc starts from aux[row] instead of 0
-template <int G2, int TAG, bool HALO, int SEG, int AUX = D16_AUX_NONE>
+// V: the value stream's type (d16_values); x, every product (double)a * x[col] and every sum are
+// fp64 and in the same order for both.
+template <int G2, int TAG, bool HALO, int SEG, int AUX, class V>
 __global__ __launch_bounds__(TPB) void k_d16_spmv(int64_t nrows, int64_t nslices, const int64_t *__restrict__ sptr,
                                                   const int64_t *__restrict__ sfirst,
                                                   const int32_t *__restrict__ slpr,
-                                                  const uint16_t *__restrict__ dl, const double *__restrict__ dv,
+                                                  const uint16_t *__restrict__ dl, const V *__restrict__ dv,
                                                   const int32_t *__restrict__ seg, const double *__restrict__ x,
                                                   double *__restrict__ y, double alpha, double beta,
                                                   const double *__restrict__ z, const double *__restrict__ ghost,
                                                   int32_t nlocal, const int32_t *__restrict__ slist,
                                                   const int32_t *__restrict__ rowmap, double *aux) {
     static_assert(SEG == 4 || SEG == 8, "segment bases are one or two int4 per lane");
+    static_assert(AUX != D16_AUX_STORE || d16_values<V>::AUX_STORE, "the raw-sum store belongs to the fp64 launch");
+    typedef typename d16_values<V>::pack pack;
+    constexpr int PER = d16_values<V>::PER, NQ = 8 / PER;  // entries per pack, packs per 8-entry group
     const int lane = threadIdx.x & 63;
     // nslices: slices this launch processes -- all of them, or the subset
     // listed in slist (interior / halo rows of a distributed product)
@@ -2810,7 +2633,7 @@ __global__ __launch_bounds__(TPB) void k_d16_spmv(int64_t nrows, int64_t nslices
     d16_i4 sb2 = sb;
     if (SEG == 8) sb2 = __builtin_nontemporal_load(reinterpret_cast<const d16_i4 *>(seg) + (sl * 64 + lane) * 2 + 1);
     const d16_u4 *dp = reinterpret_cast<const d16_u4 *>(dl + base) + lane;
-    const d16_d2 *vp = reinterpret_cast<const d16_d2 *>(dv + base) + lane;
+    const pack *vp = reinterpret_cast<const pack *>(dv + base) + lane;
     int32_t col = 0;
     int si = 0;
     double acc = 0.0;
@@ -2818,13 +2641,13 @@ __global__ __launch_bounds__(TPB) void k_d16_spmv(int64_t nrows, int64_t nslices
     const int64_t ng = L >> 3;
     for (int64_t g0 = 0; g0 < ng; g0 += G2) {
         d16_u4 d[G2];
-        d16_d2 v[G2][4];
+        pack v[G2][NQ];
 #pragma unroll
         for (int u = 0; u < G2; ++u) {
             const int64_t g = g0 + u < ng ? g0 + u : ng - 1;  // wave-uniform clamp, values masked
             d[u] = __builtin_nontemporal_load(dp + g * 64);
 #pragma unroll
-            for (int q = 0; q < 4; ++q) v[u][q] = __builtin_nontemporal_load(vp + (g * 4 + q) * 64);
+            for (int q = 0; q < NQ; ++q) v[u][q] = __builtin_nontemporal_load(vp + (g * NQ + q) * 64);
         }
 #pragma unroll
         for (int u = 0; u < G2; ++u) {
@@ -2837,7 +2660,7 @@ __global__ __launch_bounds__(TPB) void k_d16_spmv(int64_t nrows, int64_t nslices
                 if (SEG == 8 && si >= 4) b = si == 4 ? sb2.x : si == 5 ? sb2.y : si == 6 ? sb2.z : sb2.w;
                 col = dd == 0 ? b : col + dd;
                 si += dd == 0 ? 1 : 0;
-                const double a = (e & 1) ? v[u][e >> 1].y : v[u][e >> 1].x;
+                const double a = d16_values<V>::get(v[u][e / PER], e % PER);
                 if (HALO) {
                     const bool loc = col < nlocal;
                     const double xv = loc ? x[(uint32_t)col] : ghost[(uint32_t)(col - nlocal)];
@@ -2917,50 +2740,53 @@ void launch_coupling_rows(int64_t n, int64_t ns, const int64_t *rp, const int32_
 void launch_first_col(int64_t nrows, const int64_t *rp, const int32_t *ci, int32_t *c0, hipStream_t st) {
     if (nrows > 0) k_first_col<<<grid_for(nrows, TPB), TPB, 0, st>>>(nrows, rp, ci, c0);
 }
-template <int G2, int SEG, int AUX>
-static void d16_dispatch(unsigned g, hipStream_t st, int64_t nrows, int64_t ns, const int64_t *sptr,
-                         const int64_t *sfirst, const int32_t *slpr, const uint16_t *dl, const double *dv,
-                         const int32_t *seg, const double *x, double *y, double alpha, double beta, const double *z,
-                         int tag, const double *ghost, int32_t nl, const int32_t *slist, const int32_t *rm, size_t shm,
-                         double *aux) {
-    if (ghost) {
-        if (tag) k_d16_spmv<G2, 1, true, SEG, AUX><<<g, TPB, shm, st>>>(nrows, ns, sptr, sfirst, slpr, dl, dv, seg, x, y, alpha, beta, z, ghost, nl, slist, rm, aux);
-        else k_d16_spmv<G2, 0, true, SEG, AUX><<<g, TPB, shm, st>>>(nrows, ns, sptr, sfirst, slpr, dl, dv, seg, x, y, alpha, beta, z, ghost, nl, slist, rm, aux);
+// one launch of k_d16_spmv: the kernel's arguments and where it goes
+template <class V>
+struct D16Call {
+    unsigned g;
+    size_t shm;
+    hipStream_t st;
+    int64_t nrows, ns;
+    D16Streams L;
+    const V *dv;
+    const double *x;
+    double *y;
+    double alpha, beta;
+    const double *z, *ghost;
+    int32_t nl;
+    const int32_t *slist, *rm;
+    double *aux;
+};
+template <int G2, int TAG, bool HALO, int SEG, int AUX, class V>
+static void d16_go(const D16Call<V> &a) {
+    k_d16_spmv<G2, TAG, HALO, SEG, AUX, V><<<a.g, TPB, a.shm, a.st>>>(a.nrows, a.ns, a.L.sptr, a.L.sfirst, a.L.slpr,
+                                                                      a.L.dl, a.dv, a.L.seg, a.x, a.y, a.alpha, a.beta,
+                                                                      a.z, a.ghost, a.nl, a.slist, a.rm, a.aux);
+}
+// the raw-sum store serves the block PC's coupling launches (tag 0, fp64 values only), the
+// initial value the outer operator's reduced launch (tag 1); both on one rank only, plain
+// layouts (no ghost columns, no rowmap: spmv_slices / MatOp check)
+template <int G2, int SEG, class V>
+static void d16_dispatch(const D16Call<V> &a, int tag, int aux_mode) {
+    if constexpr (d16_values<V>::AUX_STORE)
+        if (aux_mode == D16_AUX_STORE) return d16_go<G2, 0, false, SEG, D16_AUX_STORE>(a);
+    if (aux_mode != D16_AUX_NONE) return d16_go<G2, 1, false, SEG, D16_AUX_INIT>(a);
+    if (a.ghost) {
+        if (tag) d16_go<G2, 1, true, SEG, D16_AUX_NONE>(a);
+        else d16_go<G2, 0, true, SEG, D16_AUX_NONE>(a);
     } else {
-        if (tag) k_d16_spmv<G2, 1, false, SEG, AUX><<<g, TPB, shm, st>>>(nrows, ns, sptr, sfirst, slpr, dl, dv, seg, x, y, alpha, beta, z, ghost, nl, slist, rm, aux);
-        else k_d16_spmv<G2, 0, false, SEG, AUX><<<g, TPB, shm, st>>>(nrows, ns, sptr, sfirst, slpr, dl, dv, seg, x, y, alpha, beta, z, ghost, nl, slist, rm, aux);
+        if (tag) d16_go<G2, 1, false, SEG, D16_AUX_NONE>(a);
+        else d16_go<G2, 0, false, SEG, D16_AUX_NONE>(a);
     }
 }
-// the raw-sum store serves the block PC's coupling launches (tag 0), the initial value the
-// outer operator's reduced launch (tag 1); both on one rank only (no ghost columns)
-template <int G2, int SEG>
-static void d16_dispatch_aux(int mode, unsigned g, hipStream_t st, int64_t nrows, int64_t ns, const int64_t *sptr,
-                             const int64_t *sfirst, const int32_t *slpr, const uint16_t *dl, const double *dv,
-                             const int32_t *seg, const double *x, double *y, double alpha, double beta,
-                             const double *z, const int32_t *slist, size_t shm, double *aux) {
-    if (mode == D16_AUX_STORE)
-        k_d16_spmv<G2, 0, false, SEG, D16_AUX_STORE><<<g, TPB, shm, st>>>(nrows, ns, sptr, sfirst, slpr, dl, dv, seg, x, y, alpha, beta, z, nullptr, 0, slist, nullptr, aux);
-    else
-        k_d16_spmv<G2, 1, false, SEG, D16_AUX_INIT><<<g, TPB, shm, st>>>(nrows, ns, sptr, sfirst, slpr, dl, dv, seg, x, y, alpha, beta, z, nullptr, 0, slist, nullptr, aux);
-}
-template <int SEG>
-static void d16_unrolled(int unroll, unsigned g, hipStream_t st, int64_t nrows, int64_t nslices, const int64_t *sptr,
-                         const int64_t *sfirst, const int32_t *slpr, const uint16_t *dl, const double *dv,
-                         const int32_t *seg, const double *x, double *y, double alpha, double beta, const double *z,
-                         int tag, const double *ghost, int32_t nl, const int32_t *slist, const int32_t *rm, size_t shm,
-                         int aux_mode, double *aux) {
-    if (aux_mode != D16_AUX_NONE) {  // (plain layouts: spmv_aux checks)
-        switch (unroll) {
-            case 1: d16_dispatch_aux<1, SEG>(aux_mode, g, st, nrows, nslices, sptr, sfirst, slpr, dl, dv, seg, x, y, alpha, beta, z, slist, shm, aux); break;
-            case 2: d16_dispatch_aux<2, SEG>(aux_mode, g, st, nrows, nslices, sptr, sfirst, slpr, dl, dv, seg, x, y, alpha, beta, z, slist, shm, aux); break;
-            default: d16_dispatch_aux<4, SEG>(aux_mode, g, st, nrows, nslices, sptr, sfirst, slpr, dl, dv, seg, x, y, alpha, beta, z, slist, shm, aux); break;
-        }
-        return;
-    }
+// unroll: 1, 2 or 4 (anything else is 4) over fp64 values; 1, 2, 4 or 8 (anything else is 8) over fp32
+template <int SEG, class V>
+static void d16_unrolled(int unroll, const D16Call<V> &a, int tag, int aux_mode) {
     switch (unroll) {
-        case 1: d16_dispatch<1, SEG, D16_AUX_NONE>(g, st, nrows, nslices, sptr, sfirst, slpr, dl, dv, seg, x, y, alpha, beta, z, tag, ghost, nl, slist, rm, shm, nullptr); break;
-        case 2: d16_dispatch<2, SEG, D16_AUX_NONE>(g, st, nrows, nslices, sptr, sfirst, slpr, dl, dv, seg, x, y, alpha, beta, z, tag, ghost, nl, slist, rm, shm, nullptr); break;
-        default: d16_dispatch<4, SEG, D16_AUX_NONE>(g, st, nrows, nslices, sptr, sfirst, slpr, dl, dv, seg, x, y, alpha, beta, z, tag, ghost, nl, slist, rm, shm, nullptr); break;
+        case 1: d16_dispatch<1, SEG>(a, tag, aux_mode); break;
+        case 2: d16_dispatch<2, SEG>(a, tag, aux_mode); break;
+        case 4: d16_dispatch<4, SEG>(a, tag, aux_mode); break;
+        default: d16_dispatch<d16_values<V>::UNROLL_MAX, SEG>(a, tag, aux_mode); break;
     }
 }
 static int d16_xcd_host = 0;
@@ -2969,17 +2795,39 @@ void set_d16_xcd(int on) {
     d16_xcd_host = on;
     if (hipMemcpyToSymbol(HIP_SYMBOL(d16_xcd_map), &on, sizeof(int)) != hipSuccess) d16_xcd_host = 0;
 }
-void launch_d16_spmv(int64_t nrows, int64_t nslices, const int64_t *sptr, const int64_t *sfirst, const int32_t *slpr,
-                     const uint16_t *dl, const double *dv, const int32_t *seg, int nsegs, const double *x, double *y,
-                     double alpha, double beta, const double *z, int tag, const double *ghost, int64_t nlocal,
-                     int unroll, hipStream_t st, const int32_t *slist, const int32_t *rowmap, size_t lds_reserve,
-                     int aux_mode, double *aux) {
+template <class V>
+static void d16_launch(int64_t nrows, int64_t nslices, const D16Streams &L, const V *dv, const double *x, double *y,
+                       double alpha, double beta, const double *z, int tag, const double *ghost, int64_t nlocal,
+                       int unroll, hipStream_t st, const int32_t *slist, const int32_t *rowmap, size_t lds_reserve,
+                       int aux_mode, double *aux) {
     if (nslices <= 0) return;
     unsigned g = grid_for(nslices, TPB / 64);
     if (d16_xcd_host) g = (g + 7) / 8 * 8;  // every XCD range the same length (surplus blocks exit)
-    const int32_t nl = (int32_t)nlocal;
-    if (nsegs == 8) d16_unrolled<8>(unroll, g, st, nrows, nslices, sptr, sfirst, slpr, dl, dv, seg, x, y, alpha, beta, z, tag, ghost, nl, slist, rowmap, lds_reserve, aux_mode, aux);
-    else d16_unrolled<4>(unroll, g, st, nrows, nslices, sptr, sfirst, slpr, dl, dv, seg, x, y, alpha, beta, z, tag, ghost, nl, slist, rowmap, lds_reserve, aux_mode, aux);
+    D16Call<V> a{g, lds_reserve, st, nrows, nslices, L, dv, x, y, alpha, beta, z, ghost, (int32_t)nlocal, slist,
+                 rowmap, aux};
+    if (aux_mode != D16_AUX_NONE) {
+        a.ghost = nullptr;
+        a.nl = 0;
+        a.rm = nullptr;
+    } else {
+        a.aux = nullptr;
+    }
+    if (L.nsegs == 8) d16_unrolled<8>(unroll, a, tag, aux_mode);
+    else d16_unrolled<4>(unroll, a, tag, aux_mode);
+}
+void launch_d16_spmv(int64_t nrows, int64_t nslices, const D16Streams &L, const double *dv, const double *x, double *y,
+                     double alpha, double beta, const double *z, int tag, const double *ghost, int64_t nlocal,
+                     int unroll, hipStream_t st, const int32_t *slist, const int32_t *rowmap, size_t lds_reserve,
+                     int aux_mode, double *aux) {
+    d16_launch(nrows, nslices, L, dv, x, y, alpha, beta, z, tag, ghost, nlocal, unroll, st, slist, rowmap, lds_reserve,
+               aux_mode, aux);
+}
+void launch_d16_spmv(int64_t nrows, int64_t nslices, const D16Streams &L, const float *dv32, const double *x, double *y,
+                     double alpha, double beta, const double *z, int tag, const double *ghost, int64_t nlocal,
+                     int unroll, hipStream_t st, const int32_t *slist, const int32_t *rowmap, size_t lds_reserve,
+                     const double *aux_init) {
+    d16_launch(nrows, nslices, L, dv32, x, y, alpha, beta, z, tag, ghost, nlocal, unroll, st, slist, rowmap,
+               lds_reserve, aux_init ? D16_AUX_INIT : D16_AUX_NONE, const_cast<double *>(aux_init));
 }
 
 // ------------------------------------------- D16 with fp32 values (low) ---
@@ -2992,7 +2840,6 @@ void launch_d16_spmv(int64_t nrows, int64_t nslices, const int64_t *sptr, const 
 // the two streams coincide and the copy needs no slice table: thread t writes float4 t from
 // double2 (t / 64) * 128 + t % 64 and the one 64 further.  *overflow = 1 when a finite value
 // rounds to an infinity.
-typedef float d16_f4 __attribute__((ext_vector_type(4)));
 __global__ __launch_bounds__(TPB) void k_d16_round_values(int64_t nquads, const double *__restrict__ dv,
                                                           float *__restrict__ dv32, int32_t *overflow) {
     const int64_t t = (int64_t)blockIdx.x * TPB + threadIdx.x;
@@ -3012,133 +2859,6 @@ __global__ __launch_bounds__(TPB) void k_d16_round_values(int64_t nquads, const 
 void launch_d16_round_values(int64_t stored, const double *dv, float *dv32, int32_t *overflow, hipStream_t st) {
     const int64_t nquads = stored / 4;  // stored is a multiple of 512
     if (nquads > 0) k_d16_round_values<<<grid_for(nquads, TPB), TPB, 0, st>>>(nquads, dv, dv32, overflow);
-}
-
-// k_d16_spmv over the fp32 value stream: the same slice, lane and segment logic, x, every
-// product (double)a32 * x[col] and every sum in fp64 and in the same order.  AUX: none, or
-// D16_AUX_INIT (the reduced outer launch; the raw sums the PC stored are fp64).
-template <int G2, int TAG, bool HALO, int SEG, int AUX = D16_AUX_NONE>
-__global__ __launch_bounds__(TPB) void k_d16_spmv_f32(int64_t nrows, int64_t nslices, const int64_t *__restrict__ sptr,
-                                                      const int64_t *__restrict__ sfirst,
-                                                      const int32_t *__restrict__ slpr,
-                                                      const uint16_t *__restrict__ dl, const float *__restrict__ dv32,
-                                                      const int32_t *__restrict__ seg, const double *__restrict__ x,
-                                                      double *__restrict__ y, double alpha, double beta,
-                                                      const double *__restrict__ z, const double *__restrict__ ghost,
-                                                      int32_t nlocal, const int32_t *__restrict__ slist,
-                                                      const int32_t *__restrict__ rowmap, const double *aux) {
-    static_assert(SEG == 4 || SEG == 8, "segment bases are one or two int4 per lane");
-    static_assert(AUX == D16_AUX_NONE || AUX == D16_AUX_INIT, "the raw-sum store belongs to the fp64 launch");
-    const int lane = threadIdx.x & 63;
-    unsigned blk = blockIdx.x;
-    if (d16_xcd_map) {
-        const unsigned per = (gridDim.x + 7) / 8;
-        blk = (blockIdx.x % 8) * per + blockIdx.x / 8;
-    }
-    const int64_t idx = __builtin_amdgcn_readfirstlane((int)(blk * (TPB / 64) + (threadIdx.x >> 6)));
-    if (idx >= nslices) return;
-    const int64_t sl = slist ? (int64_t)__builtin_amdgcn_readfirstlane(slist[idx]) : idx;
-    const int64_t base = sptr[sl];
-    const int64_t L = (sptr[sl + 1] - base) >> 6;  // multiple of 8
-    const int lpr = slpr[sl];
-    const int64_t r0 = sfirst[sl], r1 = sfirst[sl + 1];
-    const int64_t row = r0 + lane / lpr;
-    const d16_i4 sb = __builtin_nontemporal_load(reinterpret_cast<const d16_i4 *>(seg) + (sl * 64 + lane) * (SEG / 4));
-    d16_i4 sb2 = sb;
-    if (SEG == 8) sb2 = __builtin_nontemporal_load(reinterpret_cast<const d16_i4 *>(seg) + (sl * 64 + lane) * 2 + 1);
-    const d16_u4 *dp = reinterpret_cast<const d16_u4 *>(dl + base) + lane;
-    const d16_f4 *vp = reinterpret_cast<const d16_f4 *>(dv32 + base) + lane;
-    int32_t col = 0;
-    int si = 0;
-    double acc = 0.0;
-    if (AUX == D16_AUX_INIT && lpr == 1 && row < r1) acc = aux[row];
-    const int64_t ng = L >> 3;
-    for (int64_t g0 = 0; g0 < ng; g0 += G2) {
-        d16_u4 d[G2];
-        d16_f4 v[G2][2];
-#pragma unroll
-        for (int u = 0; u < G2; ++u) {
-            const int64_t g = g0 + u < ng ? g0 + u : ng - 1;  // wave-uniform clamp, values masked
-            d[u] = __builtin_nontemporal_load(dp + g * 64);
-#pragma unroll
-            for (int q = 0; q < 2; ++q) v[u][q] = __builtin_nontemporal_load(vp + (g * 2 + q) * 64);
-        }
-#pragma unroll
-        for (int u = 0; u < G2; ++u) {
-            if (g0 + u >= ng) break;
-            const uint32_t w[4] = {d[u].x, d[u].y, d[u].z, d[u].w};
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const int32_t dd = (int32_t)((w[e >> 1] >> ((e & 1) * 16)) & 0xffffu);
-                int32_t b = si == 0 ? sb.x : si == 1 ? sb.y : si == 2 ? sb.z : sb.w;
-                if (SEG == 8 && si >= 4) b = si == 4 ? sb2.x : si == 5 ? sb2.y : si == 6 ? sb2.z : sb2.w;
-                col = dd == 0 ? b : col + dd;
-                si += dd == 0 ? 1 : 0;
-                const d16_f4 vq = v[u][e >> 2];
-                const double a = (double)((e & 3) == 0 ? vq.x : (e & 3) == 1 ? vq.y : (e & 3) == 2 ? vq.z : vq.w);
-                if (HALO) {
-                    const bool loc = col < nlocal;
-                    const double xv = loc ? x[(uint32_t)col] : ghost[(uint32_t)(col - nlocal)];
-                    acc += a * xv;
-                } else {
-                    acc += a * x[(uint32_t)col];
-                }
-            }
-        }
-    }
-    if (lpr > 1) {  // wave-uniform: combine the LPR partial sums of a row
-        for (int o = 1; o < lpr; o <<= 1) acc += __shfl_xor(acc, o);
-        if (lane % lpr) return;
-    }
-    if (row < r1) {
-        const int64_t yr = rowmap ? (int64_t)rowmap[row] : row;
-        double r = alpha * acc;
-        if (beta != 0.0) r += beta * z[yr];
-        y[yr] = r;
-    }
-}
-#define D16_F32_ARGS nrows, ns, sptr, sfirst, slpr, dl, dv32, seg, x, y, alpha, beta, z, ghost, nl, slist, rm, aux
-template <int G2, int SEG>
-static void d16_f32_dispatch(unsigned g, hipStream_t st, int64_t nrows, int64_t ns, const int64_t *sptr,
-                             const int64_t *sfirst, const int32_t *slpr, const uint16_t *dl, const float *dv32,
-                             const int32_t *seg, const double *x, double *y, double alpha, double beta,
-                             const double *z, int tag, const double *ghost, int32_t nl, const int32_t *slist,
-                             const int32_t *rm, size_t shm, const double *aux) {
-    if (aux) {  // the reduced outer launch (tag 1, one rank, plain layout: MatOp::apply_after_low)
-        k_d16_spmv_f32<G2, 1, false, SEG, D16_AUX_INIT><<<g, TPB, shm, st>>>(D16_F32_ARGS);
-    } else if (ghost) {
-        if (tag) k_d16_spmv_f32<G2, 1, true, SEG><<<g, TPB, shm, st>>>(D16_F32_ARGS);
-        else k_d16_spmv_f32<G2, 0, true, SEG><<<g, TPB, shm, st>>>(D16_F32_ARGS);
-    } else {
-        if (tag) k_d16_spmv_f32<G2, 1, false, SEG><<<g, TPB, shm, st>>>(D16_F32_ARGS);
-        else k_d16_spmv_f32<G2, 0, false, SEG><<<g, TPB, shm, st>>>(D16_F32_ARGS);
-    }
-}
-#undef D16_F32_ARGS
-template <int SEG>
-static void d16_f32_unrolled(int unroll, unsigned g, hipStream_t st, int64_t nrows, int64_t ns, const int64_t *sptr,
-                             const int64_t *sfirst, const int32_t *slpr, const uint16_t *dl, const float *dv32,
-                             const int32_t *seg, const double *x, double *y, double alpha, double beta,
-                             const double *z, int tag, const double *ghost, int32_t nl, const int32_t *slist,
-                             const int32_t *rm, size_t shm, const double *aux) {
-    switch (unroll) {
-        case 1: d16_f32_dispatch<1, SEG>(g, st, nrows, ns, sptr, sfirst, slpr, dl, dv32, seg, x, y, alpha, beta, z, tag, ghost, nl, slist, rm, shm, aux); break;
-        case 2: d16_f32_dispatch<2, SEG>(g, st, nrows, ns, sptr, sfirst, slpr, dl, dv32, seg, x, y, alpha, beta, z, tag, ghost, nl, slist, rm, shm, aux); break;
-        case 4: d16_f32_dispatch<4, SEG>(g, st, nrows, ns, sptr, sfirst, slpr, dl, dv32, seg, x, y, alpha, beta, z, tag, ghost, nl, slist, rm, shm, aux); break;
-        default: d16_f32_dispatch<8, SEG>(g, st, nrows, ns, sptr, sfirst, slpr, dl, dv32, seg, x, y, alpha, beta, z, tag, ghost, nl, slist, rm, shm, aux); break;
-    }
-}
-void launch_d16_spmv_f32(int64_t nrows, int64_t nslices, const int64_t *sptr, const int64_t *sfirst,
-                         const int32_t *slpr, const uint16_t *dl, const float *dv32, const int32_t *seg, int nsegs,
-                         const double *x, double *y, double alpha, double beta, const double *z, int tag,
-                         const double *ghost, int64_t nlocal, int unroll, hipStream_t st, const int32_t *slist,
-                         const int32_t *rowmap, size_t lds_reserve, const double *aux_init) {
-    if (nslices <= 0) return;
-    unsigned g = grid_for(nslices, TPB / 64);
-    if (d16_xcd_host) g = (g + 7) / 8 * 8;
-    const int32_t nl = (int32_t)nlocal;
-    if (nsegs == 8) d16_f32_unrolled<8>(unroll, g, st, nrows, nslices, sptr, sfirst, slpr, dl, dv32, seg, x, y, alpha, beta, z, tag, ghost, nl, slist, rowmap, lds_reserve, aux_init);
-    else d16_f32_unrolled<4>(unroll, g, st, nrows, nslices, sptr, sfirst, slpr, dl, dv32, seg, x, y, alpha, beta, z, tag, ghost, nl, slist, rowmap, lds_reserve, aux_init);
 }
 
 // ============================================================ SELL/B3 ======

@@ -133,24 +133,35 @@ void launch_scatter(int64_t n, const int64_t *idx, const double *x, double *y, h
 
 // deterministic reductions: fixed grid (depends only on n)
 int reduce_blocks(int64_t n);
+// The four kernels over the Krylov basis V, stored in fp64 or (compressed-basis GMRES,
+// pls_gmres_basis single) in fp32; w and all sums fp64.  Columns 512-B aligned: ldv a multiple
+// of 64 doubles / 128 floats.
 // partial[j*NB + b] for j < k :  dot(v_j, w) ; then final into out[j]
-void launch_mdot(int64_t n, int k, const double *const *v_dev_ptrs, const double *V, int64_t ldv,
-                 const double *w, double *partial, double *out, hipStream_t st);
+void launch_mdot(int64_t n, int k, const double *V, int64_t ldv, const double *w, double *partial, double *out,
+                 hipStream_t st);
+void launch_mdot(int64_t n, int k, const float *V, int64_t ldv, const double *w, double *partial, double *out,
+                 hipStream_t st);
 void launch_dot(int64_t n, const double *x, const double *y, double *partial, double *out,
                 hipStream_t st);
 // out = ||x||_2 (sqrt of sum of squares)
 void launch_norm2(int64_t n, const double *x, double *partial, double *out, hipStream_t st);
 // w -= sum_j h[j] * V[:, j] (h on device, j < k); out = ||w||_2^2 (local) when out != null
-void launch_maxpy_norm(int64_t n, int k, const double *V, int64_t ldv, const double *h_dev,
-                       double hscale, double *w, double *partial, double *out, hipStream_t st);
+void launch_maxpy_norm(int64_t n, int k, const double *V, int64_t ldv, const double *h_dev, double *w,
+                       double *partial, double *out, hipStream_t st);
+void launch_maxpy_norm(int64_t n, int k, const float *V, int64_t ldv, const double *h_dev, double *w, double *partial,
+                       double *out, hipStream_t st);
 // one modified Gram-Schmidt step: w -= (*hprev) vprev (vprev != null), then (w, vj) over the
 // updated w, (w, w) when vj is null.  ticket != null: the last block to arrive writes the sum
 // to *out (a zeroed ticket word; one launch); else partial[block] (launch_final follows)
 void launch_mgs_step(int64_t n, const double *vprev, const double *hprev, const double *vj, double *w, double *partial,
                      double *out, unsigned *ticket, hipStream_t st);
+// (fp32 basis: no single-launch sums, ticket is null -- partial[block] always, launch_final follows)
+void launch_mgs_step(int64_t n, const float *vprev, const double *hprev, const float *vj, double *w, double *partial,
+                     double *out, unsigned *ticket, hipStream_t st);
 // y = sum_j c[j] * V[:, j] (c on device)
 void launch_lincomb(int64_t n, int k, const double *V, int64_t ldv, const double *c_dev, double *y,
                     hipStream_t st);
+void launch_lincomb(int64_t n, int k, const float *V, int64_t ldv, const double *c_dev, double *y, hipStream_t st);
 // Fischer guess, model 2 (ksp_guess_type fischer): the space's update after a solve.  X, B: the
 // stored columns (stride ldv, a multiple of 64 doubles; columns 512-B aligned), m < GUESS_MAX of
 // them; x, y = A x (16-B aligned); alpha = B^T y on the device.  Writes x - X alpha and
@@ -161,18 +172,7 @@ void launch_guess_update(int64_t n, int m, double *X, double *B, int64_t ldv, co
                          const double *x, const double *y, double *partial, double *out, hipStream_t st);
 // u *= a, v *= a (both 16-B aligned)
 void launch_scale2(int64_t n, double a, double *u, double *v, hipStream_t st);
-// Compressed-basis GMRES (pls_gmres_basis single): the same four over a basis stored in fp32
-// (ldv a multiple of 128 floats), w and all sums fp64 ...
-void launch_mdot_f32(int64_t n, int k, const float *V, int64_t ldv, const double *w, double *partial, double *out,
-                     hipStream_t st);
-void launch_maxpy_norm_f32(int64_t n, int k, const float *V, int64_t ldv, const double *h_dev, double *w,
-                           double *partial, double *out, hipStream_t st);
-// (one partial per block into partial; the caller runs launch_final)
-void launch_mgs_step_f32(int64_t n, const float *vprev, const double *hprev, const float *vj, double *w,
-                         double *partial, hipStream_t st);
-void launch_lincomb_f32(int64_t n, int k, const float *V, int64_t ldv, const double *c_dev, double *y,
-                        hipStream_t st);
-// ... and the new basis vector: vf = fl32(a w), vd = vf promoted to fp64, one pass
+// Compressed-basis GMRES: the new basis vector, vf = fl32(a w), vd = vf promoted to fp64, one pass
 void launch_scale_round(int64_t n, double a, const double *w, float *vf, double *vd, hipStream_t st);
 // TSQR step (Anderson least squares): R of each TSQR rows-per-block row chunk of the
 // m <= 16 columns, written as rows [b m, b m + m) of a column-major matrix (leading dim ldo)
@@ -286,8 +286,15 @@ void launch_coupling_rows(int64_t n, int64_t ns, const int64_t *rp, const int32_
 // raw row sums of lane-per-row slices (launch_d16_spmv's aux): stored, or the initial value
 constexpr int D16_AUX_NONE = 0, D16_AUX_STORE = 1, D16_AUX_INIT = 2;
 void launch_first_col(int64_t nrows, const int64_t *rp, const int32_t *ci, int32_t *c0, hipStream_t st);
-void launch_d16_spmv(int64_t nrows, int64_t nslices, const int64_t *sptr, const int64_t *sfirst, const int32_t *slpr,
-                     const uint16_t *dl, const double *dv, const int32_t *seg, int nsegs, const double *x, double *y,
+// the streams of a D16 layout that a launch reads beside the values (DevSELL::streams fills it)
+struct D16Streams {
+    const int64_t *sptr, *sfirst;
+    const int32_t *slpr;
+    const uint16_t *dl;
+    const int32_t *seg;
+    int nsegs;
+};
+void launch_d16_spmv(int64_t nrows, int64_t nslices, const D16Streams &L, const double *dv, const double *x, double *y,
                      double alpha, double beta, const double *z, int tag, const double *ghost, int64_t nlocal,
                      int unroll /* 8-entry groups per lane in flight: 1, 2 or 4 */, hipStream_t st,
                      const int32_t *slist = nullptr /* nslices entries: the slices to process */,
@@ -299,14 +306,12 @@ void launch_d16_spmv(int64_t nrows, int64_t nslices, const int64_t *sptr, const 
 // dv32[base + (k / 4) * 256 + lane * 4 + k % 4], rounded to nearest even from the fp64 stream
 // (stored: the layout's padded entries; *overflow = 1 when a finite value rounds to an infinity) ...
 void launch_d16_round_values(int64_t stored, const double *dv, float *dv32, int32_t *overflow, hipStream_t st);
-// ... and launch_d16_spmv over that stream: x, products and sums fp64, in the same order.
-// unroll: 1, 2, 4 or 8; aux_init != null: D16_AUX_INIT (plain layouts on one rank, tag 1)
-void launch_d16_spmv_f32(int64_t nrows, int64_t nslices, const int64_t *sptr, const int64_t *sfirst,
-                         const int32_t *slpr, const uint16_t *dl, const float *dv32, const int32_t *seg, int nsegs,
-                         const double *x, double *y, double alpha, double beta, const double *z, int tag,
-                         const double *ghost, int64_t nlocal, int unroll, hipStream_t st,
-                         const int32_t *slist = nullptr, const int32_t *rowmap = nullptr, size_t lds_reserve = 0,
-                         const double *aux_init = nullptr);
+// ... and launch_d16_spmv over that stream (the same kernel): x, products and sums fp64, in the
+// same order.  unroll: 1, 2, 4 or 8; aux_init != null: D16_AUX_INIT (plain layouts on one rank, tag 1)
+void launch_d16_spmv(int64_t nrows, int64_t nslices, const D16Streams &L, const float *dv32, const double *x, double *y,
+                     double alpha, double beta, const double *z, int tag, const double *ghost, int64_t nlocal,
+                     int unroll, hipStream_t st, const int32_t *slist = nullptr, const int32_t *rowmap = nullptr,
+                     size_t lds_reserve = 0, const double *aux_init = nullptr);
 // SELL/B3: row triples sharing one column list (FE vector fields), see kernels.hip
 void launch_triple_flags(int64_t n, const int64_t *rp, const int32_t *ci, uint8_t *flag, hipStream_t st);
 int b3_lanes_per_triple();

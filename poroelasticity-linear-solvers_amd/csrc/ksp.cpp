@@ -203,8 +203,7 @@ void KSP::run(const double *b, double *x, Ctx &c) {
         reason = CONVERGED_ITS;
     } else {
         ensure_work(c);
-        if ((type == "gmres" || type == "fgmres") && basis_single) solve_gmres_cb(b, x, c);
-        else if (type == "gmres" || type == "fgmres") solve_gmres(b, x, c);
+        if (type == "gmres" || type == "fgmres") solve_gmres(b, x, c);
         else if (type == "richardson") solve_richardson(b, x, c);
         else if (type == "chebyshev") solve_chebyshev(b, x, c);
         else if (type == "cg") device_loop_allowed() ? solve_cg_dev(b, x, c) : solve_cg(b, x, c);
@@ -287,7 +286,7 @@ void KSP::guess_form(const double *b, double *x0, Ctx &c) {
         launch_copy(n, b, gy.p, c.st);
         b = gy.p;
     }
-    launch_mdot(n, m, nullptr, gB.p, guess_ldv, b, c.partials(n, m), gd.p, c.st);
+    launch_mdot(n, m, gB.p, guess_ldv, b, c.partials(n, m), gd.p, c.st);
     c.comm->global_sum_dev(gd.p, m, c.st);
     launch_lincomb(n, m, gX.p, guess_ldv, gd.p, x0, c.st);
 }
@@ -330,12 +329,12 @@ void KSP::guess_update(const double *x, Ctx &c) {
     }
     const int m = (int)guess_m;
     double *yo = gB.p + (int64_t)m * guess_ldv, *beta = d + m + 2;
-    launch_mdot(n, m, nullptr, gB.p, guess_ldv, y, c.partials(n, m), d, c.st);
+    launch_mdot(n, m, gB.p, guess_ldv, y, c.partials(n, m), d, c.st);
     launch_dot(n, y, y, c.partials(n, 1), d + m, c.st);
     c.comm->global_sum_dev(d, m + 1, c.st);
     launch_guess_update(n, m, gX.p, gB.p, guess_ldv, d, x, y, c.partials(n, 1), d + m + 1, c.st);
     if (m > 0) {
-        launch_mdot(n, m, nullptr, gB.p, guess_ldv, yo, c.partials(n, m), beta, c.st);
+        launch_mdot(n, m, gB.p, guess_ldv, yo, c.partials(n, m), beta, c.st);
         c.comm->global_sum_dev(beta, m, c.st);
         launch_guess_update(n, m, gX.p, gB.p, guess_ldv, beta, nullptr, nullptr, c.partials(n, 1), d + m + 1, c.st);
     }
@@ -352,7 +351,7 @@ void KSP::guess_update(const double *x, Ctx &c) {
             // (the new column is orthogonal to the others to eps nu0 / nu only) and normalised again
             A->apply(xo, yo, c);
             if (basis_single) ++stat_co_double;  // (the guess products stay fp64)
-            launch_mdot(n, m, nullptr, gB.p, guess_ldv, yo, c.partials(n, m), beta, c.st);
+            launch_mdot(n, m, gB.p, guess_ldv, yo, c.partials(n, m), beta, c.st);
             c.comm->global_sum_dev(beta, m, c.st);
             launch_guess_update(n, m, gX.p, gB.p, guess_ldv, beta, nullptr, nullptr, c.partials(n, 1), d + m + 1,
                                 c.st);
@@ -442,268 +441,114 @@ KSP::~KSP() {
 // estimate is the true residual norm (right preconditioning only,
 // resolve_side_norm).  PETSc's FGMRES happy-breakdown bound differs from
 // GMRES's only below the 1e-30 cap applied here.
+//
+// Compressed-basis GMRES (<prefix>pls_gmres_basis single; Aliaga, Anzt et al., "Compressed basis
+// GMRES") is the same cycle over a basis stored in fp32.  Every basis vector is rounded once,
+// v = fl32(w / ||w||), and the operator and the PC are applied to the promoted rounded vector
+// (cbv), so the Arnoldi relation holds for the basis that is stored; w (cbw), every sum and the
+// Hessenberg matrix stay fp64.  One cycle cannot reduce the residual by much more than fp32's
+// unit roundoff, and its Givens estimate drifts from the true residual by then, hence two rules
+// for that basis (norm type not none):
+//   (a) the cycle ends once the estimate is <= basis_drop x the residual the cycle began with;
+//   (b) a positive reason from the estimate ends the cycle, not the solve: x is built, the next
+//       cycle start computes and records the true residual at the same its, and that value
+//       decides -- at its == max_it too, where a failed check is DIVERGED_ITS.
+// A forced or confirming cycle start appends one history entry, as any restart does.  With norm
+// type none the fp32 basis records and tests nothing: max_it steps, CONVERGED_ITS.
 void KSP::solve_gmres(const double *b, double *x, Ctx &c) {
     const bool flexible = type == "fgmres";
+    const bool cb = basis_single;               // the fp32 basis: rules (a) and (b), the products counted
+    const bool tested = !cb || norm != "none";  // (the double basis records and tests whatever the norm type)
+    const bool hess_kept = keep_hess && !cb;
+    // compressed operator: the Arnoldi products through the fp32 copy of A, a cycle being one step
+    // of iterative refinement that the fp64 residual of the cycle start corrects
+    const bool low = cb && operator_single;
+    if (low && !A->has_low())
+        throw Error(prefix + "pls_gmres_operator single: the operator of this solver is not a stored matrix");
+    // where the vector that becomes column k lives before it is normalised, and which vector the
+    // operator and the PC read for column k: the column of V itself, or cbw and cbv
+    auto wcol = [&](int64_t k) { return cb ? cbw.p : V.p + k * ldv; };
+    auto vcol = [&](int64_t k) { return cb ? cbv.p : V.p + k * ldv; };
+    // column k = w / nrm: in place, or rounded into Vf and promoted into cbv
+    auto normalise = [&](int64_t k, double nrm, double *w) {
+        if (cb) launch_scale_round(n, 1.0 / nrm, w, Vf.p + k * ldv, cbv.p, c.st);
+        else launch_scale(n, 1.0 / nrm, w, c.st);
+    };
     const int64_t mk = restart;
     const double haptol = 1e-30;
     std::vector<double> HH((mk + 1) * (mk + 1), 0.0), cc(mk + 1, 0.0), ss(mk + 1, 0.0), grs(mk + 2, 0.0),
         nrs(mk + 1, 0.0), hcol(mk + 1, 0.0);
     auto H = [&](int64_t i, int64_t j) -> double & { return HH[(size_t)i * (mk + 1) + j]; };
     double *t1p = t1.p, *t2p = t2.p;  // (no t1 for fgmres: right, with the PC's output in Z)
-    if (keep_hess) hess.assign((size_t)(mk + 1) * (mk + 1), 0.0);
+    if (hess_kept) hess.assign((size_t)(mk + 1) * (mk + 1), 0.0);
     launch_set(n, 0.0, x, c.st);
-    if (orthog == MGS) HIPCHK(hipMemsetAsync(mgs_ticket.p, 0, sizeof(unsigned), c.st));
-    its = 0;
-    reason = 0;
-    bool first = true;
-    while (!reason) {
-        double *v0 = V.p;
-        if (first) {
-            launch_copy(n, b, right ? v0 : t1p, c.st);
-        } else {
-            A->apply(x, t2p, c);
-            launch_waxpby(n, 1.0, b, -1.0, t2p, right ? v0 : t1p, c.st);
-        }
-        if (!right) pc->apply(t1p, v0, c);
-        double res = c.norm2(n, v0);
-        reason = record(its, res);
-        if (res == 0.0) {
-            reason = CONVERGED_ATOL;
-            break;
-        }
-        launch_scale(n, 1.0 / res, v0, c.st);
-        std::fill(HH.begin(), HH.end(), 0.0);
-        grs.assign(mk + 2, 0.0);
-        grs[0] = res;
-        int64_t loc_it = 0;
-        while (!reason && loc_it < mk && its < maxit) {
-            double *vk = V.p + loc_it * ldv;
-            double *vn = V.p + (loc_it + 1) * ldv;
-            if (right) {
-                double *zk = flexible ? Z.p + loc_it * ldv : t1p;
-                pc->apply(vk, zk, c);
-                A->apply_after(*pc, zk, vn, c);  // (may continue a product the PC has just formed with zk)
-            } else {
-                A->apply(vk, t1p, c);
-                pc->apply(t1p, vn, c);
-            }
-            const int k = (int)(loc_it + 1);
-            const double tt = std::sqrt(gmres_orthogonalise(k, vn, hcol.data(), c));
-            for (int j = 0; j < k; ++j) H(j, loc_it) = hcol[j];
-            H(loc_it + 1, loc_it) = tt;
-            if (keep_hess && first) {
-                for (int j = 0; j < k; ++j) hess[(size_t)j + (size_t)loc_it * (mk + 1)] = hcol[j];
-                hess[(size_t)k + (size_t)loc_it * (mk + 1)] = tt;
-            }
-            double hapbnd = std::fabs(tt / grs[loc_it]);
-            if (hapbnd > haptol) hapbnd = haptol;
-            const bool hapend = tt < hapbnd;
-            if (!hapend) launch_scale(n, 1.0 / tt, vn, c.st);
-            // KSPGMRESUpdateHessenberg
-            const int64_t it = loc_it;
-            for (int64_t j = 0; j < it; ++j) {
-                const double t0 = H(j, it);
-                H(j, it) = cc[j] * t0 + ss[j] * H(j + 1, it);
-                H(j + 1, it) = cc[j] * H(j + 1, it) - ss[j] * t0;
-            }
-            if (!hapend) {
-                const double t0 = std::sqrt(H(it, it) * H(it, it) + H(it + 1, it) * H(it + 1, it));
-                if (t0 == 0.0) {
-                    reason = DIVERGED_NULL;
-                    break;
-                }
-                cc[it] = H(it, it) / t0;
-                ss[it] = H(it + 1, it) / t0;
-                grs[it + 1] = -(ss[it] * grs[it]);
-                grs[it] = cc[it] * grs[it];
-                H(it, it) = cc[it] * H(it, it) + ss[it] * H(it + 1, it);
-                res = std::fabs(grs[it + 1]);
-            } else {
-                res = 0.0;
-            }
-            loc_it++;
-            its++;
-            reason = record(its, res);
-            if (hapend && !reason) {
-                reason = DIVERGED_BREAKDOWN;
-                break;
-            }
-        }
-        // KSPGMRESBuildSoln: x += M^-1 V y (right), V y (left), Z y (fgmres)
-        const int64_t it = loc_it - 1;
-        if (it >= 0) {
-            if (H(it, it) == 0.0) {
-                reason = DIVERGED_BREAKDOWN;
-            } else {
-                nrs[it] = grs[it] / H(it, it);
-                for (int64_t k = it - 1; k >= 0; --k) {
-                    double t0 = grs[k];
-                    for (int64_t j = k + 1; j <= it; ++j) t0 = t0 - H(k, j) * nrs[j];
-                    nrs[k] = t0 / H(k, k);
-                }
-                HIPCHK(hipMemcpyAsync(dh.p, nrs.data(), sizeof(double) * (it + 1), hipMemcpyHostToDevice, c.st));
-                launch_lincomb(n, (int)(it + 1), flexible ? Z.p : V.p, ldv, dh.p, t2p, c.st);
-                if (right && !flexible) {
-                    pc->apply(t2p, t1p, c);
-                    launch_axpby(n, 1.0, t1p, 1.0, x, c.st);
-                } else {
-                    launch_axpby(n, 1.0, t2p, 1.0, x, c.st);
-                }
-                c.sync();  // nrs host buffer reuse
-            }
-        }
-        if (its >= maxit) {
-            if (!reason) reason = DIVERGED_ITS;
-            break;
-        }
-        first = false;
-    }
-}
-
-// The orthogonalisation of one Arnoldi step (PETSc's gborthog.c rules), w = column k of V:
-//   CGS            h = V^T w, w -= V h in one multi-vector kernel each (refine_never);
-//                  refine_always runs the pair again on the updated w and adds the second
-//                  pass's l_j to h_j here, in double; refine_ifneeded does so exactly when
-//                  ||w|| after the first pass is smaller than sqrt(sum_j h_j^2) (j ascending)
-//   MGS            for j ascending: h_j = (w, v_j), w -= h_j v_j -- k dependent reductions,
-//                  so k + 1 launches of one step kernel (the update by h_{j-1} fused into the
-//                  launch that sums (w, v_j); the last one sums (w, w)), each reading its
-//                  coefficient from dh, where the launch before it left it.  k_final and the
-//                  global sum sit between the steps; with pls.gmres_mgs_fused, on one rank, the
-//                  last block to arrive finishes each sum in its launch instead (not the
-//                  default: 4 % slower at 10M rows, a tie at 2,669).  The
-//                  same order of summation either way: bitwise the same on one rank.
-// The k + 1 scalars come to the host in one read-back per pass.
-double KSP::gmres_orthogonalise(int k, double *w, double *h, Ctx &c) {
-    double *hs = c.host_scalars(k + 1);
-    auto read_back = [&](const double *d) {
-        HIPCHK(hipMemcpyAsync(hs, d, sizeof(double) * (k + 1), hipMemcpyDeviceToHost, c.st));
-        c.sync();
-    };
-    ++stat_orth_steps;
-    if (orthog == MGS) {
-        const bool fuse = mgs_fused && c.comm->size == 1;
-        for (int j = 0; j <= k; ++j) {
-            launch_mgs_step(n, j > 0 ? V.p + (int64_t)(j - 1) * ldv : nullptr, j > 0 ? dh.p + (j - 1) : nullptr,
-                            j < k ? V.p + (int64_t)j * ldv : nullptr, w, mgs_part.p, dh.p + j,
-                            fuse ? mgs_ticket.p : nullptr, c.st);
-            if (!fuse) {
-                launch_final(n, 1, mgs_part.p, dh.p + j, c.st);
-                c.comm->global_sum_dev(dh.p + j, 1, c.st);
-            }
-        }
-        read_back(dh.p);
-        std::copy(hs, hs + k, h);
-        return hs[k];
-    }
-    auto cgs_pass = [&](double *d) {
-        launch_mdot(n, k, nullptr, V.p, ldv, w, c.partials(n, k), d, c.st);
-        c.comm->global_sum_dev(d, k, c.st);
-        launch_maxpy_norm(n, k, V.p, ldv, d, -1.0, w, c.partials(n, 1), d + k, c.st);
-        c.comm->global_sum_dev(d + k, 1, c.st);
-        read_back(d);
-    };
-    cgs_pass(dh.p);
-    std::copy(hs, hs + k, h);
-    bool again = orthog == CGS_ALWAYS;
-    if (orthog == CGS_IFNEEDED) {
-        double hh = 0.0;
-        for (int j = 0; j < k; ++j) hh += h[j] * h[j];
-        again = std::sqrt(hs[k]) < std::sqrt(hh);
-    }
-    if (again) {
-        ++stat_orth_second;
-        cgs_pass(dh.p + k + 1);
-        for (int j = 0; j < k; ++j) h[j] += hs[j];
-    }
-    return hs[k];
-}
-
-// ------------------------------------------------- compressed-basis GMRES --
-// solve_gmres over a basis stored in fp32 (<prefix>pls_gmres_basis single; Aliaga, Anzt et al.,
-// "Compressed basis GMRES").  Every basis vector is rounded once, v = fl32(w / ||w||), and the
-// operator and the PC are applied to the promoted rounded vector (cbv), so the Arnoldi relation
-// holds for the basis that is stored; w (cbw), every sum and the Hessenberg matrix stay fp64.
-// One cycle cannot reduce the residual by much more than fp32's unit roundoff, and its Givens
-// estimate drifts from the true residual by then, hence two rules (norm type not none):
-//   (a) the cycle ends once the estimate is <= basis_drop x the residual the cycle began with;
-//   (b) a positive reason from the estimate ends the cycle, not the solve: x is built, the next
-//       cycle start computes and records the true residual at the same its, and that value
-//       decides -- at its == max_it too, where a failed check is DIVERGED_ITS.
-// A forced or confirming cycle start appends one history entry, as any restart does.  With norm
-// type none nothing is recorded or tested: max_it steps, CONVERGED_ITS.
-void KSP::solve_gmres_cb(const double *b, double *x, Ctx &c) {
-    const bool flexible = type == "fgmres", normed = norm != "none";
-    const int64_t mk = restart;
-    const double haptol = 1e-30;
-    std::vector<double> HH((mk + 1) * (mk + 1), 0.0), cc(mk + 1, 0.0), ss(mk + 1, 0.0), grs(mk + 2, 0.0),
-        nrs(mk + 1, 0.0), hcol(mk + 1, 0.0);
-    auto H = [&](int64_t i, int64_t j) -> double & { return HH[(size_t)i * (mk + 1) + j]; };
-    double *w = cbw.p, *vd = cbv.p, *t1p = t1.p, *t2p = t2.p;
-    // compressed operator: the Arnoldi products through the fp32 copy of A, a cycle being one step
-    // of iterative refinement that the fp64 residual below corrects
-    const bool low = operator_single;
-    if (low && !A->has_low())
-        throw Error(prefix + "pls_gmres_operator single: the operator of this solver is not a stored matrix");
-    launch_set(n, 0.0, x, c.st);
+    if (orthog == MGS && !cb) HIPCHK(hipMemsetAsync(mgs_ticket.p, 0, sizeof(unsigned), c.st));
     its = 0;
     reason = 0;
     bool first = true, confirming = false;
     while (true) {
+        double *w0 = wcol(0);
         if (first) {
-            launch_copy(n, b, right ? w : t1p, c.st);
+            launch_copy(n, b, right ? w0 : t1p, c.st);
         } else {
             A->apply(x, t2p, c);
-            ++stat_co_double;
-            launch_waxpby(n, 1.0, b, -1.0, t2p, right ? w : t1p, c.st);
+            if (cb) ++stat_co_double;
+            launch_waxpby(n, 1.0, b, -1.0, t2p, right ? w0 : t1p, c.st);
         }
-        if (!right) pc->apply(t1p, w, c);
-        double res = c.norm2(n, w);
-        if (normed) {
-            reason = record(its, res);
-            if (confirming) {
-                ++stat_cb_confirm;
-                if (!reason) ++stat_cb_failed;
-            }
+        if (!right) pc->apply(t1p, w0, c);
+        double res = c.norm2(n, w0);
+        if (tested) reason = record(its, res);
+        if (confirming) {
+            ++stat_cb_confirm;
+            if (!reason) ++stat_cb_failed;
         }
         confirming = false;
         if (res == 0.0) {
             reason = CONVERGED_ATOL;
             break;
         }
-        if (reason) break;
-        if (its >= maxit) {  // (a confirmation that failed at max_it, or max_it 0)
-            reason = normed ? DIVERGED_ITS : CONVERGED_ITS;
-            break;
+        if (cb) {
+            if (reason) break;
+            if (its >= maxit) {  // (a confirmation that failed at max_it, or max_it 0)
+                reason = tested ? DIVERGED_ITS : CONVERGED_ITS;
+                break;
+            }
         }
         const double res0c = res;
-        launch_scale_round(n, 1.0 / res, w, Vf.p, vd, c.st);
+        normalise(0, res, w0);
         std::fill(HH.begin(), HH.end(), 0.0);
         grs.assign(mk + 2, 0.0);
         grs[0] = res;
         int64_t loc_it = 0;
-        int creason = 0;  // the cycle's reason, from its estimates
+        int creason = reason;  // the cycle's reason, from its estimates (double basis: the cycle start's too)
         bool forced = false;
         while (!creason && !forced && loc_it < mk && its < maxit) {
+            double *vk = vcol(loc_it), *w = wcol(loc_it + 1);
             if (right) {
                 double *zk = flexible ? Z.p + loc_it * ldv : t1p;
-                pc->apply(vd, zk, c);
+                pc->apply(vk, zk, c);
+                // (may continue a product the PC has just formed with zk)
                 if (low) A->apply_after_low(*pc, zk, w, c);
                 else A->apply_after(*pc, zk, w, c);
             } else {
-                if (low) A->apply_low(vd, t1p, c);
-                else A->apply(vd, t1p, c);
+                if (low) A->apply_low(vk, t1p, c);
+                else A->apply(vk, t1p, c);
                 pc->apply(t1p, w, c);
             }
-            ++(low ? stat_co_low : stat_co_double);
+            if (cb) ++(low ? stat_co_low : stat_co_double);
             const int k = (int)(loc_it + 1);
-            const double tt = std::sqrt(gmres_orthogonalise_cb(k, w, hcol.data(), c));
+            const double tt = std::sqrt(cb ? gmres_orthogonalise(k, Vf.p, w, hcol.data(), c)
+                                           : gmres_orthogonalise(k, V.p, w, hcol.data(), c));
             for (int j = 0; j < k; ++j) H(j, loc_it) = hcol[j];
             H(loc_it + 1, loc_it) = tt;
+            if (hess_kept && first) {
+                for (int j = 0; j < k; ++j) hess[(size_t)j + (size_t)loc_it * (mk + 1)] = hcol[j];
+                hess[(size_t)k + (size_t)loc_it * (mk + 1)] = tt;
+            }
             double hapbnd = std::fabs(tt / grs[loc_it]);
             if (hapbnd > haptol) hapbnd = haptol;
             const bool hapend = tt < hapbnd;
-            if (!hapend) launch_scale_round(n, 1.0 / tt, w, Vf.p + (loc_it + 1) * ldv, vd, c.st);
+            if (!hapend) normalise(loc_it + 1, tt, w);
             // KSPGMRESUpdateHessenberg
             const int64_t it = loc_it;
             for (int64_t j = 0; j < it; ++j) {
@@ -728,13 +573,14 @@ void KSP::solve_gmres_cb(const double *b, double *x, Ctx &c) {
             }
             loc_it++;
             its++;
-            if (normed) creason = record(its, res);
+            if (tested) creason = record(its, res);
             if (hapend && !creason) {
                 creason = DIVERGED_BREAKDOWN;
                 break;
             }
             // rule (a), where the cycle would otherwise go on
-            forced = normed && !creason && basis_drop > 0.0 && res <= basis_drop * res0c && loc_it < mk && its < maxit;
+            forced = cb && tested && !creason && basis_drop > 0.0 && res <= basis_drop * res0c && loc_it < mk &&
+                     its < maxit;
         }
         // KSPGMRESBuildSoln: x += M^-1 V y (right), V y (left), Z y (fgmres; Z is fp64)
         const int64_t it = loc_it - 1;
@@ -749,8 +595,8 @@ void KSP::solve_gmres_cb(const double *b, double *x, Ctx &c) {
                     nrs[k] = t0 / H(k, k);
                 }
                 HIPCHK(hipMemcpyAsync(dh.p, nrs.data(), sizeof(double) * (it + 1), hipMemcpyHostToDevice, c.st));
-                if (flexible) launch_lincomb(n, (int)(it + 1), Z.p, ldv, dh.p, t2p, c.st);
-                else launch_lincomb_f32(n, (int)(it + 1), Vf.p, ldv, dh.p, t2p, c.st);
+                if (cb && !flexible) launch_lincomb(n, (int)(it + 1), Vf.p, ldv, dh.p, t2p, c.st);
+                else launch_lincomb(n, (int)(it + 1), flexible ? Z.p : V.p, ldv, dh.p, t2p, c.st);
                 if (right && !flexible) {
                     pc->apply(t2p, t1p, c);
                     launch_axpby(n, 1.0, t1p, 1.0, x, c.st);
@@ -761,7 +607,7 @@ void KSP::solve_gmres_cb(const double *b, double *x, Ctx &c) {
             }
         }
         first = false;
-        if (creason < 0) {
+        if (creason < 0 || (creason && !cb)) {
             reason = creason;
             break;
         }
@@ -770,16 +616,31 @@ void KSP::solve_gmres_cb(const double *b, double *x, Ctx &c) {
             continue;
         }
         if (its >= maxit) {
-            reason = normed ? DIVERGED_ITS : CONVERGED_ITS;
+            reason = tested ? DIVERGED_ITS : CONVERGED_ITS;
             break;
         }
         if (forced) ++stat_cb_forced;
     }
 }
 
-// gmres_orthogonalise over the fp32 basis: the same passes and rules, the columns read as
-// floats by the _f32 kernels (k_final after every MGS step: no single-launch sums here).
-double KSP::gmres_orthogonalise_cb(int k, double *w, double *h, Ctx &c) {
+// The orthogonalisation of one Arnoldi step (PETSc's gborthog.c rules) against the k columns of
+// the basis B -- V, or Vf read as floats and promoted:
+//   CGS            h = V^T w, w -= V h in one multi-vector kernel each (refine_never);
+//                  refine_always runs the pair again on the updated w and adds the second
+//                  pass's l_j to h_j here, in double; refine_ifneeded does so exactly when
+//                  ||w|| after the first pass is smaller than sqrt(sum_j h_j^2) (j ascending)
+//   MGS            for j ascending: h_j = (w, v_j), w -= h_j v_j -- k dependent reductions,
+//                  so k + 1 launches of one step kernel (the update by h_{j-1} fused into the
+//                  launch that sums (w, v_j); the last one sums (w, w)), each reading its
+//                  coefficient from dh, where the launch before it left it.  k_final and the
+//                  global sum sit between the steps; with pls.gmres_mgs_fused, on one rank and
+//                  over the double basis, the last block to arrive finishes each sum in its
+//                  launch instead (not the default: 4 % slower at 10M rows, a tie at 2,669;
+//                  DESIGN.md section 15).  The same order of summation either way: bitwise the
+//                  same on one rank.
+// The k + 1 scalars come to the host in one read-back per pass.
+template <class T>
+double KSP::gmres_orthogonalise(int k, const T *B, double *w, double *h, Ctx &c) {
     double *hs = c.host_scalars(k + 1);
     auto read_back = [&](const double *d) {
         HIPCHK(hipMemcpyAsync(hs, d, sizeof(double) * (k + 1), hipMemcpyDeviceToHost, c.st));
@@ -787,20 +648,24 @@ double KSP::gmres_orthogonalise_cb(int k, double *w, double *h, Ctx &c) {
     };
     ++stat_orth_steps;
     if (orthog == MGS) {
+        const bool fuse = mgs_fused && c.comm->size == 1 && !basis_single;
         for (int j = 0; j <= k; ++j) {
-            launch_mgs_step_f32(n, j > 0 ? Vf.p + (int64_t)(j - 1) * ldv : nullptr, j > 0 ? dh.p + (j - 1) : nullptr,
-                                j < k ? Vf.p + (int64_t)j * ldv : nullptr, w, mgs_part.p, c.st);
-            launch_final(n, 1, mgs_part.p, dh.p + j, c.st);
-            c.comm->global_sum_dev(dh.p + j, 1, c.st);
+            launch_mgs_step(n, j > 0 ? B + (int64_t)(j - 1) * ldv : nullptr, j > 0 ? dh.p + (j - 1) : nullptr,
+                            j < k ? B + (int64_t)j * ldv : nullptr, w, mgs_part.p, dh.p + j,
+                            fuse ? mgs_ticket.p : nullptr, c.st);
+            if (!fuse) {
+                launch_final(n, 1, mgs_part.p, dh.p + j, c.st);
+                c.comm->global_sum_dev(dh.p + j, 1, c.st);
+            }
         }
         read_back(dh.p);
         std::copy(hs, hs + k, h);
         return hs[k];
     }
     auto cgs_pass = [&](double *d) {
-        launch_mdot_f32(n, k, Vf.p, ldv, w, c.partials(n, k), d, c.st);
+        launch_mdot(n, k, B, ldv, w, c.partials(n, k), d, c.st);
         c.comm->global_sum_dev(d, k, c.st);
-        launch_maxpy_norm_f32(n, k, Vf.p, ldv, d, w, c.partials(n, 1), d + k, c.st);
+        launch_maxpy_norm(n, k, B, ldv, d, w, c.partials(n, 1), d + k, c.st);
         c.comm->global_sum_dev(d + k, 1, c.st);
         read_back(d);
     };

@@ -627,11 +627,11 @@ static void d16_product(const DevCSR &M, const DevSELL &S, int64_t count, const 
                         Ctx &c, bool low) {
     const int32_t *rm = S.nrows_mapped ? S.rowmap.p : nullptr;
     if (low)
-        launch_d16_spmv_f32(M.nrows, count, S.sptr.p, S.sfirst.p, S.slpr.p, S.dl.p, S.val32.p, S.seg.p, S.nsegs, x, y,
-                            alpha, beta, z, M.tag, ghost, nlocal, c.d16_unroll_single, c.st, slist, rm);
+        launch_d16_spmv(M.nrows, count, S.streams(), S.val32.p, x, y, alpha, beta, z, M.tag, ghost, nlocal,
+                        c.d16_unroll_single, c.st, slist, rm);
     else
-        launch_d16_spmv(M.nrows, count, S.sptr.p, S.sfirst.p, S.slpr.p, S.dl.p, S.val.p, S.seg.p, S.nsegs, x, y, alpha,
-                        beta, z, M.tag, ghost, nlocal, c.d16_unroll, c.st, slist, rm);
+        launch_d16_spmv(M.nrows, count, S.streams(), S.val.p, x, y, alpha, beta, z, M.tag, ghost, nlocal, c.d16_unroll,
+                        c.st, slist, rm);
 }
 
 void spmv(const DevCSR &M, const double *x, double *y, Ctx &c, double alpha, double beta, const double *z, bool low) {
@@ -705,17 +705,16 @@ void spmv_slices(const DevCSR &M, const double *x, double *y, Ctx &c, double alp
     if (!plain_d16(M)) throw Error("spmv_slices: plain D16 layouts only");
     if (qout && M.tag) throw Error("spmv_slices: raw row sums are stored for inner matrices only");
     const DevSELL &S = *M.sell;
-    launch_d16_spmv(M.nrows, count, S.sptr.p, S.sfirst.p, S.slpr.p, S.dl.p, S.val.p, S.seg.p, S.nsegs, x, y, alpha, beta,
-                    z, M.tag, nullptr, M.ncols, c.d16_unroll, c.st, slist, nullptr, lds_reserve,
-                    qout ? D16_AUX_STORE : D16_AUX_NONE, qout);
+    launch_d16_spmv(M.nrows, count, S.streams(), S.val.p, x, y, alpha, beta, z, M.tag, nullptr, M.ncols, c.d16_unroll,
+                    c.st, slist, nullptr, lds_reserve, qout ? D16_AUX_STORE : D16_AUX_NONE, qout);
 }
 
 void spmv_store_sums(const DevCSR &M, const double *x, double *y, Ctx &c, double alpha, double beta, const double *z,
                      double *qout) {
     if (!plain_d16(M) || M.tag) throw Error("spmv_store_sums: plain D16 layouts of inner matrices only");
     const DevSELL &S = *M.sell;
-    launch_d16_spmv(M.nrows, S.nslices, S.sptr.p, S.sfirst.p, S.slpr.p, S.dl.p, S.val.p, S.seg.p, S.nsegs, x, y, alpha,
-                    beta, z, 0, nullptr, M.ncols, c.d16_unroll, c.st, nullptr, nullptr, 0, D16_AUX_STORE, qout);
+    launch_d16_spmv(M.nrows, S.nslices, S.streams(), S.val.p, x, y, alpha, beta, z, 0, nullptr, M.ncols, c.d16_unroll,
+                    c.st, nullptr, nullptr, 0, D16_AUX_STORE, qout);
 }
 
 // ======================================================= coupling reuse ===
@@ -874,25 +873,41 @@ hipEvent_t Timers::mark(hipStream_t s) {
     return e;
 }
 
-void MatOp::apply(const double *x, double *y, Ctx &c) {
-    if (!M->sell) build_sell(const_cast<DevCSR &>(*M), c);
+// The full product: over the fp64 values, or (low) over the fp32 stream of the layout.
+void MatOp::product(const double *x, double *y, Ctx &c, bool lo) {
+    if (lo) {
+        if (!low) throw Error("MatOp::apply_low: the low-precision operator was not asked for");
+        // (a new layout: the matrix changed)
+        if (!M->sell || !M->sell->has_low()) enable_low(c, "pls_gmres_operator single");
+    } else if (!M->sell) {
+        build_sell(const_cast<DevCSR &>(*M), c);
+    }
     if (timers) timers->begin(T_SPMV);
-    spmv(*M, x, y, c);
+    spmv(*M, x, y, c, 1.0, 0.0, nullptr, lo);
     if (timers) { timers->end(T_SPMV); timers->spmv_calls++; }
     if (coupling) coupling->n_full++;
 }
 
 // The reduced product where the PC's coupling sums belong to x, else the full one.  T_SPMV
 // gets the reduced launch and the coupling launches that produced q (together they stream
-// the whole of A once), as one call.
-void MatOp::apply_after(const PC &pc, const double *x, double *y, Ctx &c) {
+// the whole of A once), as one call.  low: over the fp32 stream of A'; the reuse rows start
+// from the PC's fp64 raw sums, so their coupling entries enter with their fp64 values.
+void MatOp::product_after(const PC &pc, const double *x, double *y, Ctx &c, bool lo) {
     Coupling *R = coupling;
-    if (!R || !R->eligible || pc.coupling_product() != R || R->fresh_for != x) return apply(x, y, c);
+    if (!R || !R->eligible || pc.coupling_product() != R || R->fresh_for != x) return product(x, y, c, lo);
+    if (lo) {
+        if (!low) throw Error("MatOp::apply_after_low: the low-precision operator was not asked for");
+        if (!R->reduced.has_low()) build_low(R->reduced, c, "pls_gmres_operator single (reduced outer operator)");
+    }
     R->fresh_for = nullptr;
     const DevSELL &S = R->reduced;
     if (timers) timers->begin(T_SPMV);
-    launch_d16_spmv(M->nrows, S.nslices, S.sptr.p, S.sfirst.p, S.slpr.p, S.dl.p, S.val.p, S.seg.p, S.nsegs, x, y, 1.0,
-                    0.0, nullptr, 1, nullptr, M->ncols, c.d16_unroll, c.st, nullptr, nullptr, 0, D16_AUX_INIT, R->q.p);
+    if (lo)
+        launch_d16_spmv(M->nrows, S.nslices, S.streams(), S.val32.p, x, y, 1.0, 0.0, nullptr, 1, nullptr, M->ncols,
+                        c.d16_unroll_single, c.st, nullptr, nullptr, 0, R->q.p);
+    else
+        launch_d16_spmv(M->nrows, S.nslices, S.streams(), S.val.p, x, y, 1.0, 0.0, nullptr, 1, nullptr, M->ncols,
+                        c.d16_unroll, c.st, nullptr, nullptr, 0, D16_AUX_INIT, R->q.p);
     if (timers) {
         timers->end(T_SPMV);
         timers->spmv_calls++;
@@ -902,6 +917,10 @@ void MatOp::apply_after(const PC &pc, const double *x, double *y, Ctx &c) {
     R->spans.clear();
     R->n_reduced++;
 }
+void MatOp::apply(const double *x, double *y, Ctx &c) { product(x, y, c, false); }
+void MatOp::apply_after(const PC &pc, const double *x, double *y, Ctx &c) { product_after(pc, x, y, c, false); }
+void MatOp::apply_low(const double *x, double *y, Ctx &c) { product(x, y, c, true); }
+void MatOp::apply_after_low(const PC &pc, const double *x, double *y, Ctx &c) { product_after(pc, x, y, c, true); }
 
 // ---- the low-precision operator (compressed-operator GMRES)
 void Op::apply_low(const double *, double *, Ctx &) {
@@ -918,36 +937,6 @@ void MatOp::enable_low(Ctx &c, const std::string &who) {
 int64_t MatOp::low_bytes() const {
     return (M->sell ? M->sell->low_stream_bytes() : 0) +
            (coupling && coupling->eligible ? coupling->reduced.low_stream_bytes() : 0);
-}
-void MatOp::apply_low(const double *x, double *y, Ctx &c) {
-    if (!low) throw Error("MatOp::apply_low: the low-precision operator was not asked for");
-    if (!M->sell || !M->sell->has_low()) enable_low(c, "pls_gmres_operator single");  // (a new layout: the matrix changed)
-    if (timers) timers->begin(T_SPMV);
-    spmv(*M, x, y, c, 1.0, 0.0, nullptr, true);
-    if (timers) { timers->end(T_SPMV); timers->spmv_calls++; }
-    if (coupling) coupling->n_full++;
-}
-// apply_after over the fp32 stream of A': the reuse rows start from the PC's fp64 raw sums, so
-// their coupling entries enter with their fp64 values
-void MatOp::apply_after_low(const PC &pc, const double *x, double *y, Ctx &c) {
-    Coupling *R = coupling;
-    if (!R || !R->eligible || pc.coupling_product() != R || R->fresh_for != x) return apply_low(x, y, c);
-    if (!low) throw Error("MatOp::apply_after_low: the low-precision operator was not asked for");
-    if (!R->reduced.has_low()) build_low(R->reduced, c, "pls_gmres_operator single (reduced outer operator)");
-    R->fresh_for = nullptr;
-    const DevSELL &S = R->reduced;
-    if (timers) timers->begin(T_SPMV);
-    launch_d16_spmv_f32(M->nrows, S.nslices, S.sptr.p, S.sfirst.p, S.slpr.p, S.dl.p, S.val32.p, S.seg.p, S.nsegs, x, y,
-                        1.0, 0.0, nullptr, 1, nullptr, M->ncols, c.d16_unroll_single, c.st, nullptr, nullptr, 0,
-                        R->q.p);
-    if (timers) {
-        timers->end(T_SPMV);
-        timers->spmv_calls++;
-        if (R->spans_flush == timers->flushes)
-            for (const Timers::Span &sp : R->spans) timers->add(T_SPMV, sp);
-    }
-    R->spans.clear();
-    R->n_reduced++;
 }
 
 void Op::residual(const double *x, const double *b, double *r, Ctx &c) {

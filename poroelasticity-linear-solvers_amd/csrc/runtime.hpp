@@ -166,6 +166,7 @@ struct DevSELL {
     // Compressed-operator GMRES (pls_gmres_operator single): the D16 values once more, rounded to
     // fp32, val32[base + (k / 4) * 256 + lane * 4 + k % 4] (build_low; empty until a KSP asks)
     DBuf<float> val32;
+    D16Streams streams() const { return {sptr.p, sfirst.p, slpr.p, dl.p, seg.p, nsegs}; }  // (D16 layouts)
     bool has_low() const { return d16 && !b3_nslices && val32.p != nullptr; }
     int64_t low_stream_bytes() const { return has_low() ? stored * 4 : 0; }
     int64_t bytes_low() const { return bytes() - stored * 4; }  // bytes one low product streams (D16 only)
@@ -376,6 +377,11 @@ struct MatOp : Op {
     void apply_low(const double *x, double *y, Ctx &c) override;
     void apply_after_low(const PC &pc, const double *x, double *y, Ctx &c) override;
     int64_t low_bytes() const;  // bytes of the fp32 streams held: the layout's and the coupling's reduced one
+private:
+    // the bodies of apply / apply_low and apply_after / apply_after_low: timers, spans, fresh_for
+    // and the coupling's counters; lo picks the value stream and its unroll knob
+    void product(const double *x, double *y, Ctx &c, bool lo);
+    void product_after(const PC &pc, const double *x, double *y, Ctx &c, bool lo);
 };
 
 // --------------------------------------------------------- preconditioners --
@@ -530,7 +536,7 @@ struct KSP {
     int64_t stat_co_low = 0, stat_co_double = 0;  // low / fp64 products in solves
     int64_t basis_bytes() const { return basis_single ? (int64_t)(Vf.n * sizeof(float)) : (int64_t)(V.n * sizeof(double)); }
     // GMRES: keep the Hessenberg columns of the first cycle as Arnoldi made them (the cycle
-    // rotates its own copy in place): hess[i + j * (restart + 1)], column j = step j
+    // rotates its own copy in place): hess[i + j * (restart + 1)], column j = step j (double basis only)
     bool keep_hess = false;
     std::vector<double> hess;
     // richardson, chebyshev (left, zero initial guess, no inner products unless a norm is asked for)
@@ -588,13 +594,11 @@ struct KSP {
     void guess_update(const double *x, Ctx &c);
     void check_guess_bounds(Ctx &c);
     hipEvent_t guess_ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    void solve_gmres(const double *b, double *x, Ctx &c);  // gmres and fgmres
-    // one Arnoldi step: w orthogonalised against the first k columns of V; the Hessenberg
-    // column's k entries into h (host), ||w||^2 returned
-    double gmres_orthogonalise(int k, double *w, double *h, Ctx &c);
-    // the same cycle and step over the fp32 basis (basis_single)
-    void solve_gmres_cb(const double *b, double *x, Ctx &c);
-    double gmres_orthogonalise_cb(int k, double *w, double *h, Ctx &c);
+    void solve_gmres(const double *b, double *x, Ctx &c);  // gmres and fgmres, over V or (basis_single) Vf
+    // one Arnoldi step: w orthogonalised against the first k columns of the basis B (V.p or
+    // Vf.p); the Hessenberg column's k entries into h (host), ||w||^2 returned
+    template <class T>
+    double gmres_orthogonalise(int k, const T *B, double *w, double *h, Ctx &c);
     void check_basis_bounds(Ctx &c);
     void solve_cg(const double *b, double *x, Ctx &c);
     void solve_cg_dev(const double *b, double *x, Ctx &c);
