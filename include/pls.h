@@ -303,6 +303,18 @@ int pls_get_chebyshev_bounds(pls_handle *h, const char *prefix, double out[4]);
  * it (the factors' entries), [3] the longest filled row.  With k = 0, [2] = [1].
  * An unknown prefix, or a PC that is not ILU / BJACOBI(ILU), is an error.     */
 int pls_get_ilu_fill(pls_handle *h, const char *prefix, int64_t stats[4]);
+/* The overlapping additive Schwarz PC (<prefix>pc_type asm) of the KSP with this
+ * prefix: stats[0] blocks (<prefix>pc_asm_blocks), [1] overlap
+ * (<prefix>pc_asm_overlap), [2] <prefix>pc_asm_type as 0 restrict, 1 basic,
+ * 2 interpolate, 3 none, [3] the rows of all subdomains together, [4] the rows
+ * of the largest, [5] 1 when the fused kernel serves the application (the
+ * subdomains fit LDS and pls.asm_fused is not 0), else 0.  An unknown prefix,
+ * or a PC that is not asm, is an error.                                      */
+int pls_get_asm_stats(pls_handle *h, const char *prefix, int64_t stats[6]);
+/* Its subdomains: ptr[blocks + 1] offsets into rows[stats[3]], each subdomain's
+ * rows ascending, numbered within the block the prefix solves (field-major
+ * order).  rows may be NULL to read the offsets alone.                       */
+int pls_get_asm_rows(pls_handle *h, const char *prefix, int64_t *ptr, int32_t *rows);
 /* Eigenvalues of the leading m x m part (1 <= m <= 64) of an upper Hessenberg
  * matrix stored by columns, H[i + j * ldh]; entries below the subdiagonal are
  * not read.  Host code (shifted QR, no LAPACK, no device): re[k] + i im[k], in

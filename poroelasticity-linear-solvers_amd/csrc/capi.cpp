@@ -755,6 +755,36 @@ int pls_get_ilu_fill(pls_handle *hh, const char *prefix, int64_t *stats) {
         stats[3] = ilu->F.max_row;
     })
 }
+static const PCASM *find_asm(Handle &H, const char *prefix, const void *out, const std::string &who) {
+    const KSP *found = find_ksp(H, prefix, out, who);
+    const PCASM *a = dynamic_cast<const PCASM *>(found->pc);
+    if (!a)
+        throw Error(who + ": the PC with prefix '" + found->prefix + "' is of type " +
+                    (found->pc ? found->pc->type : std::string("none")) + ", not asm");
+    return a;
+}
+int pls_get_asm_stats(pls_handle *hh, const char *prefix, int64_t *stats) {
+    PLS_TRY({
+        const PCASM *a = find_asm(*reinterpret_cast<Handle *>(hh), prefix, stats, "pls_get_asm_stats");
+        stats[0] = a->nblocks;
+        stats[1] = a->overlap;
+        stats[2] = (int64_t)a->atype;
+        stats[3] = a->ne;
+        stats[4] = a->largest;
+        stats[5] = a->fused ? 1 : 0;
+    })
+}
+int pls_get_asm_rows(pls_handle *hh, const char *prefix, int64_t *ptr, int32_t *rows) {
+    PLS_TRY({
+        Handle &H = *reinterpret_cast<Handle *>(hh);
+        const PCASM *a = find_asm(H, prefix, ptr, "pls_get_asm_rows");
+        std::copy(a->ptr_h.begin(), a->ptr_h.end(), ptr);
+        if (rows && a->ne) {
+            H.ctx.sync();
+            HIPCHK(hipMemcpy(rows, a->gidx.p, sizeof(int32_t) * a->ne, hipMemcpyDeviceToHost));
+        }
+    })
+}
 int pls_hessenberg_eigenvalues(int m,const double *H, int ldh, double *re, double *im) {
     return hessenberg_eigenvalues(m, H, ldh, re, im);
 }

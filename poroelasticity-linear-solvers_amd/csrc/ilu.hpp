@@ -173,4 +173,34 @@ struct PCILU : PC {
     void print_profile(const DBuf<int64_t> &prof, Ctx &c);  // pls.sweep_profile
 };
 
+// PCASM on one rank (asm.cpp, asm.hip): bjacobi's contiguous ranges grown by `overlap` rounds of
+// MatIncreaseOverlap_SeqAIJ, A_b = M[I_b, I_b] factored by ILU(levels).  The subdomain matrices
+// are the diagonal blocks of one extended matrix E (sum |I_b| rows), which an inner PCILU with
+// explicit block bounds factors and sweeps; apply() gathers x into the extended vector (input
+// mask), runs the inner sweep and combines (output mask) -- or, where the inner sweep is the
+// plain LDS one, runs all three in one launch (k_asm_blocks_lds).
+struct PCASM : PC {
+    enum Type { Restrict = 0, Basic = 1, Interpolate = 2, None = 3 };  // pls_get_asm_stats' numbering
+    PCASM(const DevCSR &M, const Options &o, const std::string &prefix, Ctx &c);
+    // scratch vectors are per stream (as PCILU::ring_scratch), so two streams may apply at once
+    bool reentrant() const override { return inner->reentrant(); }
+    void apply(const double *x, double *y, Ctx &c) override;
+    const PC *unwrapped() const override { return inner.get(); }  // pls_get_ilu_fill reports the factors
+    int64_t nblocks = 1, overlap = 1, ne = 0, largest = 0;  // ne: sum |I_b|
+    Type atype = Restrict;
+    bool fused = false;  // k_asm_blocks_lds serves apply()
+    bool mask_in() const { return atype == Interpolate || atype == None; }
+    bool mask_out() const { return atype == Restrict || atype == None; }
+    std::vector<int64_t> ptr_h;  // nblocks + 1 offsets of the subdomains in the extended numbering
+    DBuf<int64_t> ptr;
+    DBuf<int32_t> gidx;   // global row of each extended row (the subdomains, each ascending)
+    DBuf<uint8_t> own;    // 1 where the extended row's block owns the global row
+    DBuf<int32_t> opos;   // per global row: its owned extended position
+    DBuf<int64_t> tptr;   // per global row: its extended positions, ascending block order (CSR)
+    DBuf<int32_t> tpos;
+    std::unique_ptr<PCILU> inner;
+    struct Scratch { DBuf<double> xe, ye, xc; };
+    std::map<hipStream_t, Scratch> scratch;
+};
+
 }  // namespace pls

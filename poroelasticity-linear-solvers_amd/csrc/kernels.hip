@@ -3925,6 +3925,66 @@ void launch_ilu_blocks_lds(int64_t n, int64_t nblocks, const int64_t *Lgoff, con
                                                         Ugslice, Usptr, Ucol, Uval, Ulpr, x, y, prof, rr, bstart, blk_hi);
 }
 
+// Additive Schwarz over LDS-resident subdomains (PCASM, asm.cpp): k_ilu_blocks_lds<false> with the
+// gather and the restricted scatter in the workgroup.  Block blk's extended rows are
+// [bstart[blk], bstart[blk + 1]); extended row e is global row gidx[e], own[e] = 1 where the block
+// owns it.  Load: ys[t] = x[gidx[e]], 0.0 where the type masks the input and the row is not
+// owned.  The sweeps are sweep_block's, with k_ilu_blocks_lds's arguments: the same bits.  Store:
+// direct -- owned rows to y[gidx[e]] (every global row has exactly one owner: no race, no
+// atomics); else every row to y[e], the extended vector that k_asm_combine sums.  x must not be
+// y when direct: another workgroup reads the overlap rows this one overwrites (PCASM copies x).
+// gidx and own lie inside [0, n) / the extended range by construction (k_asm_grow).
+__global__ __launch_bounds__(1024) void k_asm_blocks_lds(
+    int64_t nblocks, const int64_t *__restrict__ bstart, const int64_t *__restrict__ Lgoff,
+    const int64_t *__restrict__ Lgslice, const int64_t *__restrict__ Lsptr, const int32_t *__restrict__ Lcol,
+    const double *__restrict__ Lval, const int32_t *__restrict__ Llpr, const int64_t *__restrict__ Ugoff,
+    const int64_t *__restrict__ Ugslice, const int64_t *__restrict__ Usptr, const int32_t *__restrict__ Ucol,
+    const double *__restrict__ Uval, const int32_t *__restrict__ Ulpr, const int32_t *__restrict__ gidx,
+    const uint8_t *__restrict__ own, int mask_in, int direct, const double *__restrict__ x, double *__restrict__ y,
+    int rr) {
+    extern __shared__ __attribute__((aligned(16))) double lds_y[];
+    const int64_t blk = nblocks - 1 - (int64_t)blockIdx.x;
+    const int64_t b0 = bstart[blk], len = bstart[blk + 1] - b0;
+    double *ys = lds_y;
+    const int lane = threadIdx.x & 63;
+    const int wave = threadIdx.x >> 6;
+    const int nw = blockDim.x >> 6;
+    for (int64_t t = threadIdx.x; t < len; t += blockDim.x) {
+        const int64_t e = b0 + t;
+        ys[t] = (mask_in && !own[e]) ? 0.0 : x[gidx[e]];
+    }
+    __syncthreads();
+    sweep_block<SW_P, false, false, 2>(Lgoff[blk], Lgoff[blk + 1], Llpr[blk], lane, wave, nw, false, Lgslice, Lsptr,
+                                       Lcol, Lval, ys, nullptr, nullptr, 0, 0, 0, {}, rr);
+    sweep_block<SW_P, false, false, 2>(Ugoff[blk], Ugoff[blk + 1], Ulpr[blk], lane, wave, nw, true, Ugslice, Usptr,
+                                       Ucol, Uval, ys, nullptr, nullptr, 0, 0, 0, {}, rr);
+    for (int64_t t = threadIdx.x; t < len; t += blockDim.x) {
+        const int64_t e = b0 + t;
+        if (!direct) y[e] = ys[t];
+        else if (own[e]) y[gidx[e]] = ys[t];
+    }
+}
+
+void launch_asm_blocks_lds(int64_t nblocks, const int64_t *bstart, int64_t max_len, const int64_t *Lgoff,
+                           const int64_t *Lgslice, const int64_t *Lsptr, const int32_t *Lcol, const double *Lval,
+                           const int32_t *Llpr, const int64_t *Ugoff, const int64_t *Ugslice, const int64_t *Usptr,
+                           const int32_t *Ucol, const double *Uval, const int32_t *Ulpr, const int32_t *gidx,
+                           const uint8_t *own, int mask_in, int direct, const double *x, double *y, int tpb, int rr,
+                           hipStream_t st) {
+    if (nblocks <= 0) return;
+    if (tpb < 64 || tpb > 1024 || (tpb & 63)) tpb = 1024;
+    static bool configured = false;
+    if (!configured) {
+        (void)hipFuncSetAttribute((const void *)k_asm_blocks_lds, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)163840);
+        configured = true;
+    }
+    const size_t bytes = (size_t)max_len * 8;  // (PCASM: max_len <= ilu_lds_max_rows(), the inner sweep is Lds)
+    k_asm_blocks_lds<<<(unsigned)nblocks, tpb, bytes, st>>>(nblocks, bstart, Lgoff, Lgslice, Lsptr, Lcol, Lval, Llpr,
+                                                            Ugoff, Ugslice, Usptr, Ucol, Uval, Ulpr, gidx, own,
+                                                            mask_in, direct, x, y, rr);
+}
+
 // ======================================================= chain sweep ====
 // Blocks whose level DAG is deep and narrow -- FE rows in their natural
 // order, ~2-3 rows per level: the classical AMG's hybrid Gauss-Seidel chunks

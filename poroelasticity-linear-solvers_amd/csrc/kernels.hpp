@@ -556,4 +556,37 @@ void launch_spike_apply(int64_t n, int64_t nb, int64_t bw, int upper, int64_t pl
                         double *scratch, hipStream_t st);
 int64_t spike_scratch_doubles(int64_t bw);  // scratch of launch_spike_apply
 
+// --------------------------------------- overlapping additive Schwarz (asm.hip) --
+// Subdomain growth: `grid` workgroups (at most ASM_GROW_GRID), each with 3 x nw words of `bits`
+// (nw = (n + 31) / 32; zero on entry, left zero).  fill false: cnt[b] = |I_b|; fill true:
+// rows[ptr[b] ..] = I_b ascending and own = 1 on the rows of the block's own range.
+static constexpr int ASM_GROW_GRID = 256;
+void launch_asm_grow(bool fill, int grid, int64_t n, int64_t nb, int overlap, const int64_t *rp, const int32_t *ci,
+                     unsigned *bits, int64_t nw, int64_t *cnt, const int64_t *ptr, int32_t *rows, uint8_t *own,
+                     hipStream_t st);
+// The extended matrix: row e = row rows[e] of M restricted to its block's set, columns renumbered to
+// extended positions (ascending).  fill false: len[e]; fill true: eci / eval at erp[e].
+void launch_asm_extend(bool fill, int64_t ne, int64_t n, int64_t nb, const int64_t *ptr, const int32_t *rows,
+                       const int64_t *rp, const int32_t *ci, const double *val, int64_t *len, const int64_t *erp,
+                       int32_t *eci, double *eval, hipStream_t st);
+// Per global row its extended positions in ascending block order (tptr from the scan of cnt), and
+// opos[r], the position that owns row r.
+void launch_asm_transpose_count(int64_t ne, const int32_t *rows, const uint8_t *own, int64_t *cnt, int32_t *opos,
+                                hipStream_t st);
+void launch_asm_transpose_fill(int64_t ne, int64_t n, const int32_t *rows, const int64_t *tptr, int32_t *cursor,
+                               int32_t *tpos, hipStream_t st);
+void launch_asm_gather(int64_t ne, const int32_t *gidx, const uint8_t *own, int mask_in, const double *x, double *xe,
+                       hipStream_t st);
+void launch_asm_combine(int64_t n, int mask_out, const int32_t *opos, const int64_t *tptr, const int32_t *tpos,
+                        const double *ye, double *y, hipStream_t st);
+// The fused application over LDS-resident subdomains (kernels.hip, beside k_ilu_blocks_lds whose
+// sweep_block it calls): gather through gidx with the input mask, both sweeps, then owned rows
+// straight to y[gidx[e]] (direct) or every row to y[e] (the extended vector; k_asm_combine follows).
+void launch_asm_blocks_lds(int64_t nblocks, const int64_t *bstart, int64_t max_len, const int64_t *Lgoff,
+                           const int64_t *Lgslice, const int64_t *Lsptr, const int32_t *Lcol, const double *Lval,
+                           const int32_t *Llpr, const int64_t *Ugoff, const int64_t *Ugslice, const int64_t *Usptr,
+                           const int32_t *Ucol, const double *Uval, const int32_t *Ulpr, const int32_t *gidx,
+                           const uint8_t *own, int mask_in, int direct, const double *x, double *y, int tpb, int rr,
+                           hipStream_t st);
+
 }  // namespace pls

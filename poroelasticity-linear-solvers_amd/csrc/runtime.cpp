@@ -1435,6 +1435,8 @@ std::unique_ptr<PC> make_pc(const std::string &type, const DevCSR &M, const Opti
         if (sub == "none") return std::make_unique<PCNone>(M.nrows);
         throw Error(prefix + "sub_pc_type " + sub + " is not available on the device");
     }
+    // overlapping additive Schwarz on one rank (asm.cpp; refuses a sharded matrix itself)
+    if (type == "asm") return std::make_unique<PCASM>(M, o, prefix, c);
     if (type == "gamg") return make_amg(M, o, prefix, false, c);
     if (type == "hypre") {
         // hypre is not in this image: classical AMG restating BoomerAMG as the
@@ -1448,7 +1450,7 @@ std::unique_ptr<PC> make_pc(const std::string &type, const DevCSR &M, const Opti
         return make_boomeramg(M, o, prefix, c);
     }
     throw Error("PC type '" + type + "' (prefix " + prefix +
-                ") is not available in this build (supported: none, jacobi, ilu, bjacobi, lu, gamg, hypre)");
+                ") is not available in this build (supported: none, jacobi, ilu, bjacobi, asm, lu, gamg, hypre)");
 }
 
 // =========================================================== fieldsplit ===

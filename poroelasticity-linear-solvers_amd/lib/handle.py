@@ -323,6 +323,23 @@ class Handle:
         N.check(N.lib().pls_get_ilu_fill(self.ptr, prefix.encode(), N.ptr(s)))
         return tuple(int(v) for v in s)
 
+    def asm_stats(self, prefix):
+        """(blocks, overlap, type as 0 restrict / 1 basic / 2 interpolate / 3 none, rows of all
+        subdomains together, rows of the largest, 1 when the fused kernel serves the application)
+        of the asm PC with this options prefix (pls_get_asm_stats)."""
+        s = np.zeros(6, dtype=np.int64)
+        N.check(N.lib().pls_get_asm_stats(self.ptr, prefix.encode(), N.ptr(s)))
+        return tuple(int(v) for v in s)
+
+    def asm_rows(self, prefix):
+        """(ptr int64[blocks + 1], rows int32): the subdomains of the asm PC with this options
+        prefix, each ascending, numbered within the prefix's block (pls_get_asm_rows)."""
+        s = self.asm_stats(prefix)
+        ptr = np.zeros(s[0] + 1, dtype=np.int64)
+        rows = np.zeros(max(s[3], 1), dtype=np.int32)
+        N.check(N.lib().pls_get_asm_rows(self.ptr, prefix.encode(), N.ptr(ptr), N.ptr(rows)))
+        return ptr, rows[:s[3]]
+
     def reuse_stats(self):
         """(reduced outer products, full outer products since the last reset_timings, eligible 0/1)
         of the coupling reuse (pls_get_reuse_stats)."""
