@@ -119,7 +119,22 @@ int pls_set_device(int device);
  * rule; built on the device); k = 0, the default, is ILU(0).  A negative or
  * non-integer k is an error that names the key; so are a filled row longer
  * than the factorization stages and a filled pattern beyond the free device
- * memory.  pls_get_ilu_fill reports the fill.                                */
+ * memory.  pls_get_ilu_fill reports the fill.
+ * Dirichlet columns: "<prefix>pls_bc_columns keep | lift | drop" for the inner
+ * prefixes s_ f_ p_ diff_ fp_ fp_fieldsplit_{0,1}_ (keep, the default, builds
+ * nothing; any other value is an error that lists the three).  A row of the
+ * block whose stored diagonal is 1.0 exactly and whose other stored values are
+ * all 0.0 is a constrained row, as dolfin's bc.apply leaves it.  lift and drop
+ * give the KSP a copy K' of its block with every value in a constrained column
+ * outside that column's own row set to 0.0 (the pattern is kept); operator, PC
+ * and SpMV layout are built from K'.  lift also keeps the moved nonzeros C and
+ * starts every solve of that KSP with b' = b - C b, which solves the block as
+ * given: K^-1 b = K'^-1 (b - C b).  drop applies no correction and is another
+ * preconditioner.  Refused, naming the key: a KSP that was handed its PC (fp_
+ * over a fieldsplit: use fp_fieldsplit_{0,1}_), an operator that is not a
+ * stored matrix (the Schur split), operator and preconditioner matrices that
+ * differ, a sharded block.  pls_update_matrices detects and splits again.
+ * pls_get_bc_columns_stats / pls_get_bc_columns_matrix report the split.     */
 
 /* Build a solver from host CSR matrices in the caller's (e.g. dolfin
  * interleaved) ordering plus the field index sets (sorted global indices of
@@ -315,6 +330,20 @@ int pls_get_asm_stats(pls_handle *h, const char *prefix, int64_t stats[6]);
  * rows ascending, numbered within the block the prefix solves (field-major
  * order).  rows may be NULL to read the offsets alone.                       */
 int pls_get_asm_rows(pls_handle *h, const char *prefix, int64_t *ptr, int32_t *rows);
+/* The Dirichlet-column split (<prefix>pls_bc_columns) of the KSP with this
+ * prefix: stats[0] the mode, 0 keep, 1 lift, 2 drop, [1] the constrained rows
+ * found, [2] the entries moved to C, [3] the rows of C, [4] the bytes the KSP
+ * holds for K', C and (lift) the row map and b'.  With keep [1]-[4] are 0; a
+ * block in which nothing moves is not copied ([4] is then the row list's
+ * 4 x [1] bytes).  Sets the preconditioner up if
+ * it was not yet.  An unknown prefix is an error.                             */
+int pls_get_bc_columns_stats(pls_handle *h, const char *prefix, int64_t stats[5]);
+/* The split itself: bc_rows[stats[1]] the constrained rows, ascending; C as CSR
+ * over all rows of the block, c_rp[n + 1], c_ci[stats[2]], c_val[stats[2]],
+ * columns ascending.  Rows and columns are numbered within the block the prefix
+ * solves (field-major order).  Any pointer may be NULL.                       */
+int pls_get_bc_columns_matrix(pls_handle *h, const char *prefix, int32_t *bc_rows, int64_t *c_rp, int32_t *c_ci,
+                              double *c_val);
 /* Eigenvalues of the leading m x m part (1 <= m <= 64) of an upper Hessenberg
  * matrix stored by columns, H[i + j * ldh]; entries below the subdiagonal are
  * not read.  Host code (shifted QR, no LAPACK, no device): re[k] + i im[k], in

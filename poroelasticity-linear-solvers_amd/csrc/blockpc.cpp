@@ -2,6 +2,7 @@
 // sub-blocks and inner solvers, the 2-way and 3-way applies, the 2-way
 // pressure-first pipeline.
 #include "blockpc.hpp"
+#include "bccols.hpp"
 
 #include <algorithm>
 #include <chrono>
@@ -365,6 +366,9 @@ void BlockPC::choose_concurrent_3way(const Inputs &in) {
     for (KSP *k : {ksp_s.get(), ksp_f.get(), ksp_p.get(), ksp_pd.get()}) pre = pre && k && k->type == "preonly";
     // the s and f PCs serve both sweeps at once: they must be reentrant
     for (KSP *k : {ksp_s.get(), ksp_f.get()}) pre = pre && k->pc && k->pc->reentrant();
+    // ... and so must their solves: a lifting KSP (pls_bc_columns lift) forms b' in one buffer of its own
+    // (p_ and diff_ each solve on one stream only)
+    for (KSP *k : {ksp_s.get(), ksp_f.get()}) pre = pre && !(k->bc && k->bc->lifting());
     if (!pre) return;
     second_stream();
     ensure_event(ev_in);
@@ -396,6 +400,7 @@ void BlockPC::setup_fp_pipeline(const Inputs &in) {
     if (three_way || in.distributed || mode == 0) return;
     if (!ksp_fp || ksp_fp->type != "preonly" || mixer.order > 0) return;
     if (ksp_fp->monitor) return;  // -fp_ksp_monitor: the plain path's KSP::solve prints it
+    if (ksp_fp->bc && ksp_fp->bc->lifting()) return;  // fp_pls_bc_columns lift: KSP::solve forms b' first
     if (mode < 0 && !(ksp_s && ksp_s->type == "preonly" && dynamic_cast<PCILU *>(ksp_s->pc))) return;
     PCILU *pc = dynamic_cast<PCILU *>(ksp_fp->pc);
     if (!pc || !pc->can_apply_blocks() || pc->nblocks < 8 || pc->block_levels_h.size() != (size_t)pc->nblocks) return;

@@ -12,6 +12,7 @@
 #include "runtime.hpp"
 #include "amg_host.hpp"
 #include "anderson.hpp"
+#include "bccols.hpp"
 #include "blockpc.hpp"
 #include "dist.hpp"
 #include "synthetic.hpp"
@@ -782,6 +783,51 @@ int pls_get_asm_rows(pls_handle *hh, const char *prefix, int64_t *ptr, int32_t *
         if (rows && a->ne) {
             H.ctx.sync();
             HIPCHK(hipMemcpy(rows, a->gidx.p, sizeof(int32_t) * a->ne, hipMemcpyDeviceToHost));
+        }
+    })
+}
+int pls_get_bc_columns_stats(pls_handle *hh, const char *prefix, int64_t stats[5]) {
+    PLS_TRY({
+        Handle &H = *reinterpret_cast<Handle *>(hh);
+        if (!prefix || !stats) throw Error("pls_get_bc_columns_stats: null argument");
+        ensure_ready(H);  // (the split is made when the inner solvers are)
+        const BcColumns *bc = find_ksp(H, prefix, stats, "pls_get_bc_columns_stats")->bc.get();
+        stats[0] = bc ? bc->mode : 0;
+        stats[1] = bc ? bc->nbc : 0;
+        stats[2] = bc ? bc->nmoved : 0;
+        stats[3] = bc ? bc->nrc : 0;
+        stats[4] = bc ? bc->bytes() : 0;
+    })
+}
+int pls_get_bc_columns_matrix(pls_handle *hh, const char *prefix, int32_t *bc_rows, int64_t *c_rp, int32_t *c_ci,
+                              double *c_val) {
+    PLS_TRY({
+        Handle &H = *reinterpret_cast<Handle *>(hh);
+        if (!prefix) throw Error("pls_get_bc_columns_matrix: null argument");
+        ensure_ready(H);
+        const KSP *found = find_ksp(H, prefix, prefix, "pls_get_bc_columns_matrix");
+        const BcColumns *bc = found->bc.get();
+        H.ctx.sync();
+        if (bc_rows && bc && bc->nbc)
+            HIPCHK(hipMemcpy(bc_rows, bc->bc_rows.p, sizeof(int32_t) * bc->nbc, hipMemcpyDeviceToHost));
+        if (c_rp) {
+            // the compact rows spread over all rows of the block
+            const int64_t n = found->n, nrc = bc ? bc->nrc : 0;
+            std::vector<int32_t> rows(nrc);
+            std::vector<int64_t> rp(nrc + 1, 0);
+            if (nrc) {
+                HIPCHK(hipMemcpy(rows.data(), bc->crow.p, sizeof(int32_t) * nrc, hipMemcpyDeviceToHost));
+                HIPCHK(hipMemcpy(rp.data(), bc->crp.p, sizeof(int64_t) * (nrc + 1), hipMemcpyDeviceToHost));
+            }
+            int64_t k = 0;
+            for (int64_t i = 0; i <= n; ++i) {
+                while (k < nrc && rows[k] < i) ++k;
+                c_rp[i] = rp[k];
+            }
+        }
+        if (bc && bc->nmoved) {
+            if (c_ci) HIPCHK(hipMemcpy(c_ci, bc->cci.p, sizeof(int32_t) * bc->nmoved, hipMemcpyDeviceToHost));
+            if (c_val) HIPCHK(hipMemcpy(c_val, bc->cval.p, sizeof(double) * bc->nmoved, hipMemcpyDeviceToHost));
         }
     })
 }

@@ -13,6 +13,7 @@
 // BiCGStab's run on the device unless something needs each iteration on the
 // host (KSP::device_loop_allowed).
 #include "runtime.hpp"
+#include "bccols.hpp"
 
 #include <algorithm>
 #include <chrono>
@@ -183,6 +184,8 @@ int KSP::record(int it, double r, bool test) {
 }
 
 void KSP::solve(const double *b, double *x, Ctx &c) {
+    // pls_bc_columns lift: b' = b - C b first; the guess, the norms and the test below all see b'
+    if (bc && bc->lifting()) b = bc->lift(b, c);
     history.clear();
     if (guess_nonzero || guess_fischer) solve_guessed(b, x, c);
     else run(b, x, c);
@@ -424,6 +427,8 @@ void KSP::check_basis_bounds(Ctx &c) {
             throw Error("pls.debug_bounds: the canary behind the fp32 Krylov basis (" + prefix +
                         ") was overwritten at byte +" + std::to_string(i));
 }
+
+KSP::KSP() = default;
 
 KSP::~KSP() {
     for (hipEvent_t e : guess_ev)
@@ -1344,6 +1349,31 @@ std::unique_ptr<KSP> make_ksp(const std::string &prefix, const Options &o, const
         k->cheb_steps = o.integer(prefix + "ksp_chebyshev_esteig_steps", 10);
         if (k->cheb_steps < 1 || k->cheb_steps > 64)
             throw Error(who + prefix + "ksp_chebyshev_esteig_steps must be between 1 and 64");
+    }
+    {
+        // the Dirichlet columns of a bc.apply block (bccols.hpp): with lift or drop the operator, the PC and
+        // the SpMV layout below are all built from the KSP's own K'
+        const std::string key = prefix + "pls_bc_columns", how = o.str(key, "keep");
+        if (how != "keep" && how != "lift" && how != "drop")
+            throw Error(key + ": unknown value '" + how + "' (keep, lift, drop)");
+        if (how != "keep") {
+            if (external_pc)
+                throw Error(key + " " + how + ": this solver was handed its preconditioner (the fp_ solver over a " +
+                            "fieldsplit, the outer solver over the block preconditioner); set the option on the " +
+                            "solvers inside it (fp_fieldsplit_0_, fp_fieldsplit_1_, s_, ...)");
+            if (!Amat)
+                throw Error(key + " " + how + ": the operator of this solver is not a stored matrix (the Schur " +
+                            "complement of a fieldsplit)");
+            if (Amat != Pmat)
+                throw Error(key + " " + how + ": the operator and the preconditioner matrix of this solver differ");
+            if (Amat->halo)
+                throw Error(key + " " + how + ": the block is sharded over " +
+                            std::to_string(c.comm ? c.comm->size : 1) +
+                            " ranks, and a constrained column may be owned by another rank");
+            k->bc = std::make_unique<BcColumns>();
+            k->bc->build(*Amat, how == "lift" ? BcColumns::LIFT : BcColumns::DROP, key, c);
+            if (k->bc->has_copy()) Amat = Pmat = &k->bc->Kp;
+        }
     }
     if (Amat) {
         auto op = std::make_unique<MatOp>(Amat);

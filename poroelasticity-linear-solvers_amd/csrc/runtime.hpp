@@ -468,6 +468,8 @@ void boomeramg_host_level(const HostCSR &A, const Options &o, const std::string 
                           int64_t &nlevels, int64_t &n, int64_t &nc, std::vector<int8_t> &cf, HostCSR &P);
 
 // ---------------------------------------------------------------------- KSP --
+struct BcColumns;  // bccols.hpp: the Dirichlet-column split a KSP may own (pls_bc_columns)
+
 enum Reason {
     CONVERGED_ITERATING = 0, CONVERGED_RTOL = 2, CONVERGED_ATOL = 3, CONVERGED_ITS = 4,
     DIVERGED_NULL = -2, DIVERGED_ITS = -3, DIVERGED_DTOL = -4, DIVERGED_BREAKDOWN = -5,
@@ -483,6 +485,9 @@ struct KSP {
     std::string norm = "preconditioned";
     Op *A = nullptr;
     PC *pc = nullptr;
+    // <prefix>pls_bc_columns lift | drop: K' and C of the block this KSP was given;
+    // null with keep.  In front of the PC and the operator, which are built from K' and go first.
+    std::unique_ptr<BcColumns> bc;
     std::unique_ptr<PC> owned_pc;
     std::unique_ptr<Op> owned_op;
     int64_t n = 0;
@@ -498,7 +503,7 @@ struct KSP {
     double t_start = 0;
     int64_t stat_its = 0, stat_max = 0, stat_solves = 0, stat_div = 0;  // stat_div: solves with reason < 0
     int64_t stat_last_neg = 0;  // the most recent negative reason
-    KSP() = default;
+    KSP();  // (out of line, as the destructor: bc's type is complete in ksp.cpp only)
     KSP(const KSP &) = delete;
     ~KSP();
     // work

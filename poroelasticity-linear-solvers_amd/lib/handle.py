@@ -340,6 +340,31 @@ class Handle:
         N.check(N.lib().pls_get_asm_rows(self.ptr, prefix.encode(), N.ptr(ptr), N.ptr(rows)))
         return ptr, rows[:s[3]]
 
+    def bc_columns_stats(self, prefix):
+        """(mode: 0 keep, 1 lift, 2 drop; constrained rows; entries moved to C; rows of C; bytes the
+        KSP holds for K' and C) of the inner solver with this options prefix (<prefix>pls_bc_columns,
+        pls_get_bc_columns_stats).  Sets the preconditioner up if it was not yet."""
+        s = np.zeros(5, dtype=np.int64)
+        N.check(N.lib().pls_get_bc_columns_stats(self.ptr, prefix.encode(), N.ptr(s)))
+        return tuple(int(v) for v in s)
+
+    def bc_columns_matrix(self, prefix):
+        """(bc_rows int32, c_rp int64[n + 1], c_ci int32, c_val float64): the constrained rows of
+        the block this prefix solves and the moved entries C as CSR over all its rows, numbered
+        within the block (pls_get_bc_columns_matrix)."""
+        sizes = {"s_": self.ns, "f_": self.nf, "p_": self.np, "diff_": self.np, "fp_": self.nf + self.np,
+                 "fp_fieldsplit_0_": self.np, "fp_fieldsplit_1_": self.nf}
+        if prefix not in sizes:
+            raise ValueError(f"Handle.bc_columns_matrix: no inner solver with prefix {prefix!r}")
+        s = self.bc_columns_stats(prefix)
+        rows = np.zeros(max(s[1], 1), dtype=np.int32)
+        rp = np.zeros(sizes[prefix] + 1, dtype=np.int64)
+        ci = np.zeros(max(s[2], 1), dtype=np.int32)
+        v = np.zeros(max(s[2], 1), dtype=np.float64)
+        N.check(N.lib().pls_get_bc_columns_matrix(self.ptr, prefix.encode(), N.ptr(rows), N.ptr(rp), N.ptr(ci),
+                                                  N.ptr(v)))
+        return rows[:s[1]], rp, ci[:s[2]], v[:s[2]]
+
     def reuse_stats(self):
         """(reduced outer products, full outer products since the last reset_timings, eligible 0/1)
         of the coupling reuse (pls_get_reuse_stats)."""

@@ -132,6 +132,9 @@ def run_case(problem: str, N: int, pc: str, optset: str, nranks: int, extra: dic
         if st[0]:
             inner[pre] = {"solves": st[0], "its": st[1], "max": st[2], "negative_reason": st[3],
                           "last_negative": st[4]}
+            bc = h.bc_columns_stats(pre)  # <prefix>pls_bc_columns: mode, rows, moved, rows of C, bytes
+            if bc[0]:
+                inner[pre]["bc_columns"] = list(bc)
     hist = solver.history
     out = {"problem": problem, "N": N, "pc_type": pc, "options": optset, "np": nranks, "dofs": int(s.A.shape[0]),
            "nnz": int(s.A.nnz), "its": int(solver.getIterationNumber()), "reason": int(solver.getConvergedReason()),
