@@ -1,5 +1,5 @@
 // asm.cpp -- PCASM: PETSc's overlapping additive Schwarz on one rank (pc_type asm; kernels in
-// asm.hip, the fused application in kernels.hip).  DESIGN.md section 24.
+// asm.hip, the fused application in sweep_lds.hip).  DESIGN.md section 24.
 //
 // Setup, all on the device: grow the subdomains (count, scan, fill), build the extended
 // block-diagonal matrix E = diag(M[I_b, I_b]) (count, scan, fill) and the transpose map of the

@@ -166,7 +166,7 @@ static void build_tri_sell(const PCILU &P, const PCILU::Setup &s, const TriLevel
     c.sync();
 }
 
-// LDS-kernel stream layout (kernels.hip, "LDS sweep stream layout"): per block
+// LDS-kernel stream layout (sweep_lds.hip, "LDS sweep stream layout"): per block
 // the lanes per row (1, 2 or 4) that fit every lane's share of the block's
 // longest row into the kernel's register window; slices of 64 / LPR rows of
 // one level; one header entry per lane.  Returns the most lanes per row of any block.
@@ -749,7 +749,7 @@ static int64_t build_chain_tri(const PCILU::Setup &s, const TriLevels &t, const 
     const bool upper = t.upper;
     const int64_t nblk = (int64_t)bst.size() - 1;
     const int W = ilu_lds_lane_entries(), LMAX = ilu_chain_max_lpr();
-    const int32_t PAD = (1 << 18) - 1;  // kernels.hip SW_ROW_PAD
+    const int32_t PAD = (1 << 18) - 1;  // devutil.hpp SW_ROW_PAD
     auto rlen = [&](int64_t i) -> int64_t { return upper ? rp[i + 1] - dg[i] - 1 : dg[i] - rp[i]; };
     const bool dry = D == nullptr;
     std::vector<int64_t> base(nblk, 0), nsl(nblk, 0), soff(nblk, 0);

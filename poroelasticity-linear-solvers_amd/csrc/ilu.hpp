@@ -5,7 +5,7 @@
 
 namespace pls {
 
-// Level-aligned SELL-64 strict triangular factor (see kernels.hip).
+// Level-aligned SELL-64 strict triangular factor (see sweep_lds.hip).
 struct TriSELL {
     int64_t nslices = 0, ngroups = 0, nblocks = 0;
     bool blockwise = false;
@@ -22,7 +22,7 @@ struct LdsTri {
     DBuf<int32_t> col, lpr;      // lpr: lanes per row, per block
     DBuf<double> val;
 };
-// Ring sweep tables of one triangle (kernels.hip, k_ilu_blocks_ring)
+// Ring sweep tables of one triangle (sweep_lds.hip, k_ilu_blocks_ring)
 struct RingTri {
     DBuf<int64_t> coff, cg, cp;  // chunks per block / first level / [start, end) positions
     DBuf<int32_t> ord;           // position -> row (the triangle's level order)

@@ -1,4 +1,4 @@
-// kernels.hpp -- host launchers of the HIP/CDNA4 kernels (kernels.hip).
+// kernels.hpp -- host launchers of the HIP/CDNA4 kernels (kernels.hip, sweep_lds.hip).
 // Every launcher enqueues on `st` and never synchronises.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -48,7 +48,6 @@ void launch_extract_fill(const int64_t *rp, const int32_t *ci, const double *val
                          int32_t *out_ci, double *out_val, hipStream_t st);
 
 // y = alpha * (M x) + beta * z     (z may be null when beta == 0)
-void set_spmv_short_rows(bool on);  // CSR rows of < 12 entries: one lane per row (default off; pls.spmv_short 1, opt-in)
 void launch_spmv(int64_t nrows, int64_t nnz, const int64_t *rp, const int32_t *ci,
                  const double *val, const double *x, double *y, double alpha, double beta,
                  const double *z, hipStream_t st);
@@ -326,14 +325,14 @@ void set_d16_xcd(int on);
 void launch_row_has_ghost(int64_t nrows, const int64_t *rp, const int32_t *ci, int64_t nlocal, uint8_t *flag,
                           hipStream_t st);
 
-// Level-aligned SELL-64 triangular factors (see kernels.hip)
+// Level-aligned SELL-64 triangular factors (see sweep_lds.hip)
 void launch_tri_fill(int64_t nslices, const int32_t *slot_row, const int32_t *slot_len, const int64_t *rp,
                      const int32_t *ci, const double *lu, const int64_t *diag, const double *dinv, int upper,
                      const int64_t *sptr, int32_t *ocol, double *oval, double *odinv, hipStream_t st);
 void launch_tri_blocks(int64_t nblocks, const int64_t *goff, const int64_t *gslice, const int64_t *sptr,
                        const int32_t *slot_row, const int32_t *slot_len, const int32_t *col, const double *val,
                        const double *sdinv, const double *b, double *y, hipStream_t st);
-// one level of a triangular sweep from the factored CSR, 16 lanes per row (kernels.hip)
+// one level of a triangular sweep from the factored CSR, 16 lanes per row (sweep_lds.hip)
 void launch_tri_csr_level(int64_t m, const int32_t *rows, const int64_t *rp, const int32_t *ci, const double *val,
                           const int64_t *diag, const double *dinv, int upper, const double *b, double *y,
                           hipStream_t st);
@@ -404,14 +403,12 @@ void launch_ilu_blocks_window(int64_t n, int64_t nblocks, const int64_t *bstart,
 int window_records(int max_entries);  // stream records per wave and window (4, 6, 8) for that many entries
 // (depth: windows of data in flight, 2 or 3; pls.window_depth; the ring variant: 2;
 // tri (ring variant): 1 the L sweep, 2 the U sweep on y (holding L's solution), 3 both)
-// The ring sweep (kernels.hip, k_ilu_blocks_ring): blocks of narrow levels whose
+// The ring sweep (sweep_lds.hip, k_ilu_blocks_ring): blocks of narrow levels whose
 // every level has <= ilu_ring_chunk() rows; per triangle chunk tables (coff per
 // block, cg first level, cp [start, end) positions), level orders ordL / ordU
 // (position -> row), mapUL (U position -> yL index), scratch yL / yU (n each).
 int ilu_ring_slots();
 int ilu_ring_lane_entries();  // factor entries per lane per pipeline slot of the ring sweep
-void set_ilu0_probe(int v);  // diagnostics only (pls.ilu0_probe)
-void set_ring_probe(int v);  // diagnostics only (pls.ring_probe)
 int ilu_ring_chunk();
 void launch_ilu_blocks_ring(int64_t n, int64_t nblocks, const int64_t *Lgoff, const int64_t *Lgslice,
                             const int64_t *Lsptr, const int32_t *Lcol, const double *Lval, const int32_t *Llpr,
@@ -579,7 +576,7 @@ void launch_asm_gather(int64_t ne, const int32_t *gidx, const uint8_t *own, int 
                        hipStream_t st);
 void launch_asm_combine(int64_t n, int mask_out, const int32_t *opos, const int64_t *tptr, const int32_t *tpos,
                         const double *ye, double *y, hipStream_t st);
-// The fused application over LDS-resident subdomains (kernels.hip, beside k_ilu_blocks_lds whose
+// The fused application over LDS-resident subdomains (sweep_lds.hip, beside k_ilu_blocks_lds whose
 // sweep_block it calls): gather through gidx with the input mask, both sweeps, then owned rows
 // straight to y[gidx[e]] (direct) or every row to y[e] (the extended vector; k_asm_combine follows).
 void launch_asm_blocks_lds(int64_t nblocks, const int64_t *bstart, int64_t max_len, const int64_t *Lgoff,

@@ -1,5 +1,5 @@
 // Micro-benchmark: per-level cost of the block-Jacobi LDS sweep's skeleton on
-// one workgroup of 1024 threads (diagnostics for kernels.hip sweep2).
+// one workgroup of 1024 threads (diagnostics for sweep_lds.hip sweep2).
 //   mode 0: __syncthreads() only
 //   mode 1: + 2 waves do 7 dependent-address LDS reads and one LDS write
 //   mode 2: + every wave issues 16 global loads per level, consumed 2 levels later
