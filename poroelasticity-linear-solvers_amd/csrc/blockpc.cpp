@@ -484,6 +484,7 @@ void BlockPC::setup_fp_pipeline(const Inputs &in) {
             HIPCHK(hipStreamDestroy(cx->st));
             cx->st = s;
             cx->d16_unroll = c.d16_unroll;
+            cx->d16_xcd = c.d16_xcd;
             return cx;
         };
         F.c_p = masked(mp);

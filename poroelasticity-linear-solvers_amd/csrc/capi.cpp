@@ -72,6 +72,7 @@ struct Handle {
             ctx.d16_wide_lpr != 16 && ctx.d16_wide_lpr != 32 && ctx.d16_wide_lpr != 64)
             throw Error("pls.d16_wide_lpr must be a power of two <= 64");
         ctx.d16_unroll = (int)opt.integer("pls.d16_unroll", 4);
+        ctx.d16_xcd = (int)opt.integer("pls.d16_xcd", 0);  // workgroup -> slice order (tuning)
         ctx.d16_unroll_single = (int)opt.integer("pls.d16_unroll_single", 8);  // the fp32-value kernel's depth
         if (ctx.d16_unroll_single != 1 && ctx.d16_unroll_single != 2 && ctx.d16_unroll_single != 4 &&
             ctx.d16_unroll_single != 8)
@@ -79,7 +80,6 @@ struct Handle {
         ctx.halo_overlap = opt.flag("pls.halo_overlap", true);
         ctx.d16_segs = (int)opt.integer("pls.d16_segs", D16_SEG);  // 8: force the halo layout (tests)
         if (ctx.d16_segs != D16_SEG && ctx.d16_segs != D16_SEG_MAX) throw Error("pls.d16_segs must be 4 or 8");
-        set_d16_xcd((int)opt.integer("pls.d16_xcd", 0));  // process-wide (tuning)
         ctx.d16_sigma = (int)opt.integer("pls.d16_sigma", 1024);
         if (ctx.d16_sigma < 0 || ctx.d16_sigma % 64) throw Error("pls.d16_sigma must be a multiple of 64 (0: off)");
         ctx.d16_sigma_pad = opt.num("pls.d16_sigma_pad", 0.15);

@@ -1102,7 +1102,6 @@ void PCILU::factor(const DevCSR &M, int64_t nb, Ctx &c, const Config &cfg, Setup
         const int64_t max_staged = *std::max_element(ms.begin(), ms.end());
         DBuf<int32_t> rowsL(std::max<int64_t>(n, 1));
         HIPCHK(hipMemcpyAsync(rowsL.p, ordL.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice, c.st));
-        set_ilu0_test_caps(c.ilu0_stage_cap, c.ilu_dep_grid);  // (process-wide: set per factorization)
         // one launch where levels are narrow (FE blocks: ~30 rows per level); wide levels
         // (BJACOBI on the headline: thousands of rows per level) keep a launch per level,
         // which there costs less than the per-row flags (setup 1.42 vs 1.73 s at N = 59)
@@ -1122,16 +1121,15 @@ void PCILU::factor(const DevCSR &M, int64_t nb, Ctx &c, const Config &cfg, Setup
                                     std::to_string(i) + " before its pivot row " + std::to_string(ci[k]) + ")");
             DBuf<int32_t> done(std::max<int64_t>(n, 1)), ctr(2);
             launch_ilu0_dep(n, rowsL.p, F.rp.p, F.ci.p, F.val.p, diag.p, dinv.p, fail.p, F.max_row, max_staged,
-                            done.p, ctr.p, c.st);
+                            c.ilu0_stage_cap, c.ilu_dep_grid, done.p, ctr.p, c.st);
             HIPCHK(hipGetLastError());
             c.sync();  // (done / ctr freed below)
         } else {
             for (int64_t l = 0; l < nlev_L; ++l)
                 launch_ilu0_level(Lptr[l + 1] - Lptr[l], rowsL.p + Lptr[l], F.rp.p, F.ci.p, F.val.p, diag.p, dinv.p,
-                                  fail.p, F.max_row, max_staged, c.st);
+                                  fail.p, F.max_row, max_staged, c.ilu0_stage_cap, c.st);
         }
         HIPCHK(hipGetLastError());
-        set_ilu0_test_caps(-1, 0);  // (launches above are enqueued with their plan: knobs off for other users)
         HIPCHK(hipMemcpyAsync(&hfail, fail.p, sizeof(int32_t), hipMemcpyDeviceToHost, c.st));
         c.sync();
     }

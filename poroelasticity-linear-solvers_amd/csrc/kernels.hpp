@@ -1,4 +1,4 @@
-// kernels.hpp -- host launchers of the HIP/CDNA4 kernels (kernels.hip, sweep_lds.hip).
+// kernels.hpp -- host launchers of the HIP/CDNA4 kernels (kernels.hip, ilu0.hip, sweep_lds.hip).
 // Every launcher enqueues on `st` and never synchronises.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -178,25 +178,49 @@ void launch_scale_round(int64_t n, double a, const double *w, float *vf, double 
 int tsqr_rows_per_block();
 void launch_tsqr(int64_t n, int m, const double *const *cols_dev, double *Rout, int64_t ldo, hipStream_t st);
 
-// -------------------------------------------------------------------- ILU --
+// ------------------------------------- ILU(0), level tables, level sweeps (ilu0.hip) --
 // Factor the rows of one level in place (original CSR): lu, diag pos, dinv.
 // max_row: longest row of the matrix (<= ilu0_max_row(); staged in LDS).
 int ilu0_max_row();
 // max_staged: the most upper-part entries of one row's pivots (LDS sizing)
+// test knobs (pls.ilu0_stage, pls.ilu_dep_grid): stage_cap < 0 default,
+// 0 no staged pivots, > 0 at most that many staged entries; grid_cap > 0 caps
+// k_ilu0_dep's persistent grid (1: one workgroup), 0 none
 void launch_ilu0_level(int64_t nrows_level, const int32_t *rows, const int64_t *rp,
                        const int32_t *ci, double *lu, const int64_t *diag, double *dinv,
-                       int32_t *fail, int64_t max_row, int64_t max_staged, hipStream_t st);
+                       int32_t *fail, int64_t max_row, int64_t max_staged, int stage_cap, hipStream_t st);
 // all levels in one launch (rows in level order; done: n flags, ctr: 2 ints -- scratch)
 void launch_ilu0_dep(int64_t n, const int32_t *rows, const int64_t *rp, const int32_t *ci, double *lu,
                      const int64_t *diag, double *dinv, int32_t *fail, int64_t max_row, int64_t max_staged,
-                     int32_t *done, int32_t *ctr, hipStream_t st);
-// test knobs (process-wide; pls.ilu0_stage, pls.ilu_dep_grid): stage_cap < 0 default,
-// 0 no staged pivots, > 0 at most that many staged entries; grid_cap > 0 caps
-// k_ilu0_dep's persistent grid (1: one workgroup)
-void set_ilu0_test_caps(int stage_cap, int grid_cap);
+                     int stage_cap, int grid_cap, int32_t *done, int32_t *ctr, hipStream_t st);
 void launch_find_diag(int64_t n, const int64_t *rp, const int32_t *ci, int64_t *diag, int32_t *fail,
                       hipStream_t st);
-// ILU(k) symbolic phase (iluk.hip): the pattern of the levels-of-fill factorization from one
+// Symmetric Gauss-Seidel "factors" in ILU(0) storage (hypre relax type 6 as a
+// preconditioner M = (D + L) D^-1 (D + U)): strict-lower entries scaled by the
+// column's 1/a_jj (the unit lower factor I + L D^-1), diagonal and upper kept
+// (the upper factor D + U), dinv = 1/a_ii; fail |= 2 on a zero diagonal.
+void launch_sgs_factor(int64_t n, const int64_t *rp, const int32_t *ci, double *lu, const int64_t *diag,
+                       double *dinv, int32_t *fail, hipStream_t st);
+// Level-ordered triangular factor storage ("row r of level order"): build
+void launch_lvl_count(int64_t n, const int32_t *order, const int64_t *rp, const int64_t *diag,
+                      int upper, int64_t *len, hipStream_t st);
+void launch_lvl_fill(int64_t n, const int32_t *order, const int64_t *rp, const int32_t *ci,
+                     const double *lu, const int64_t *diag, int upper, const int64_t *out_rp,
+                     int32_t *out_ci, double *out_val, hipStream_t st);
+// One level of the forward (unit lower) sweep: y[i] = b[i] - sum l_ij y[j]
+// One level of the backward sweep:           y[i] = (y[i] - sum u_ij y[j]) * dinv[i]
+void launch_trsv_level(int64_t r0, int64_t r1, const int32_t *row_of, const int64_t *rp,
+                       const int32_t *ci, const double *val, const double *dinv_lvl,
+                       const double *b, double *y, int lanes_per_row, hipStream_t st);
+
+// Block-Jacobi sweep: blocks independent, one workgroup per block.
+// blk_off[b]..blk_off[b+1] index lvl_ptr (row boundaries of block b's levels).
+void launch_trsv_blocks(int64_t nblocks, const int64_t *blk_off, const int64_t *lvl_ptr, const int32_t *row_of,
+                        const int64_t *rp, const int32_t *ci, const double *val, const double *dinv_lvl,
+                        const double *b, double *y, int lanes_per_row, hipStream_t st);
+
+// ------------------------------------------------- ILU(k) symbolic phase (iluk.hip) --
+// The pattern of the levels-of-fill factorization from one
 // breadth-first search per row of G(A) (U parts) and of G(A^T) (L parts, by columns).
 struct IlukSearch {
     int64_t n;          // searches of the whole launch: rows 0 .. n - 1
@@ -225,30 +249,8 @@ void launch_iluk_sort_rows(int64_t n, const int64_t *rp, int32_t *ci, int64_t ma
 // the block's values into the filled pattern (dval zeroed; fail |= 4: an entry without a place)
 void launch_iluk_scatter(int64_t n, const int64_t *srp, const int32_t *sci, const double *sval, const int64_t *drp,
                          const int32_t *dci, double *dval, int32_t *fail, hipStream_t st);
-// Symmetric Gauss-Seidel "factors" in ILU(0) storage (hypre relax type 6 as a
-// preconditioner M = (D + L) D^-1 (D + U)): strict-lower entries scaled by the
-// column's 1/a_jj (the unit lower factor I + L D^-1), diagonal and upper kept
-// (the upper factor D + U), dinv = 1/a_ii; fail |= 2 on a zero diagonal.
-void launch_sgs_factor(int64_t n, const int64_t *rp, const int32_t *ci, double *lu, const int64_t *diag,
-                       double *dinv, int32_t *fail, hipStream_t st);
-// Level-ordered triangular factor storage ("row r of level order"): build
-void launch_lvl_count(int64_t n, const int32_t *order, const int64_t *rp, const int64_t *diag,
-                      int upper, int64_t *len, hipStream_t st);
-void launch_lvl_fill(int64_t n, const int32_t *order, const int64_t *rp, const int32_t *ci,
-                     const double *lu, const int64_t *diag, int upper, const int64_t *out_rp,
-                     int32_t *out_ci, double *out_val, hipStream_t st);
-// One level of the forward (unit lower) sweep: y[i] = b[i] - sum l_ij y[j]
-// One level of the backward sweep:           y[i] = (y[i] - sum u_ij y[j]) * dinv[i]
-void launch_trsv_level(int64_t r0, int64_t r1, const int32_t *row_of, const int64_t *rp,
-                       const int32_t *ci, const double *val, const double *dinv_lvl,
-                       const double *b, double *y, int lanes_per_row, hipStream_t st);
 
-// Block-Jacobi sweep: blocks independent, one workgroup per block.
-// blk_off[b]..blk_off[b+1] index lvl_ptr (row boundaries of block b's levels).
-void launch_trsv_blocks(int64_t nblocks, const int64_t *blk_off, const int64_t *lvl_ptr, const int32_t *row_of,
-                        const int64_t *rp, const int32_t *ci, const double *val, const double *dinv_lvl,
-                        const double *b, double *y, int lanes_per_row, hipStream_t st);
-
+// ------------------- SpMV layouts, block sweeps (kernels.hip, sweep_lds.hip) --
 // SELL-64 (sliced ELLPACK, slice = 64 rows = one wave)
 int64_t sell_nslices(int64_t nrows);
 void launch_sell_slice_len(int64_t nrows, const int64_t *rp, int64_t *slen /* nslices+1 */, hipStream_t st);
@@ -295,7 +297,10 @@ struct D16Streams {
 };
 void launch_d16_spmv(int64_t nrows, int64_t nslices, const D16Streams &L, const double *dv, const double *x, double *y,
                      double alpha, double beta, const double *z, int tag, const double *ghost, int64_t nlocal,
-                     int unroll /* 8-entry groups per lane in flight: 1, 2 or 4 */, hipStream_t st,
+                     int unroll /* 8-entry groups per lane in flight: 1, 2 or 4 */,
+                     int d16_xcd /* workgroup -> slice order: 0 round-robin over the 8 XCDs, 1 XCD-contiguous
+                                    ranges (pls.d16_xcd); it sets the grid rounding and the kernel's map */,
+                     hipStream_t st,
                      const int32_t *slist = nullptr /* nslices entries: the slices to process */,
                      const int32_t *rowmap = nullptr /* slice position -> row (SELL-C-sigma) */,
                      size_t lds_reserve = 0 /* dynamic LDS per workgroup, unused: keeps the product's
@@ -309,8 +314,8 @@ void launch_d16_round_values(int64_t stored, const double *dv, float *dv32, int3
 // same order.  unroll: 1, 2, 4 or 8; aux_init != null: D16_AUX_INIT (plain layouts on one rank, tag 1)
 void launch_d16_spmv(int64_t nrows, int64_t nslices, const D16Streams &L, const float *dv32, const double *x, double *y,
                      double alpha, double beta, const double *z, int tag, const double *ghost, int64_t nlocal,
-                     int unroll, hipStream_t st, const int32_t *slist = nullptr, const int32_t *rowmap = nullptr,
-                     size_t lds_reserve = 0, const double *aux_init = nullptr);
+                     int unroll, int d16_xcd, hipStream_t st, const int32_t *slist = nullptr,
+                     const int32_t *rowmap = nullptr, size_t lds_reserve = 0, const double *aux_init = nullptr);
 // SELL/B3: row triples sharing one column list (FE vector fields), see kernels.hip
 void launch_triple_flags(int64_t n, const int64_t *rp, const int32_t *ci, uint8_t *flag, hipStream_t st);
 int b3_lanes_per_triple();
@@ -319,8 +324,6 @@ void launch_b3_fill(int64_t nslices, int64_t ntrip, const int64_t *bptr, const i
 void launch_b3_spmv(int64_t nslices, int64_t ntrip, const int64_t *bptr, const int32_t *tmap, const int32_t *bcol,
                     const double *bval, const double *x, double *y, double alpha, double beta, const double *z,
                     int tag, hipStream_t st);
-// D16 SpMV workgroup -> slice order: 0 round-robin over the 8 XCDs (default), 1 XCD-contiguous ranges
-void set_d16_xcd(int on);
 // flag[r] = 1 when row r (sorted columns) references a ghost column (>= nlocal)
 void launch_row_has_ghost(int64_t nrows, const int64_t *rp, const int32_t *ci, int64_t nlocal, uint8_t *flag,
                           hipStream_t st);

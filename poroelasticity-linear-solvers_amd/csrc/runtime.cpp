@@ -628,10 +628,10 @@ static void d16_product(const DevCSR &M, const DevSELL &S, int64_t count, const 
     const int32_t *rm = S.nrows_mapped ? S.rowmap.p : nullptr;
     if (low)
         launch_d16_spmv(M.nrows, count, S.streams(), S.val32.p, x, y, alpha, beta, z, M.tag, ghost, nlocal,
-                        c.d16_unroll_single, c.st, slist, rm);
+                        c.d16_unroll_single, c.d16_xcd, c.st, slist, rm);
     else
         launch_d16_spmv(M.nrows, count, S.streams(), S.val.p, x, y, alpha, beta, z, M.tag, ghost, nlocal, c.d16_unroll,
-                        c.st, slist, rm);
+                        c.d16_xcd, c.st, slist, rm);
 }
 
 void spmv(const DevCSR &M, const double *x, double *y, Ctx &c, double alpha, double beta, const double *z, bool low) {
@@ -706,7 +706,7 @@ void spmv_slices(const DevCSR &M, const double *x, double *y, Ctx &c, double alp
     if (qout && M.tag) throw Error("spmv_slices: raw row sums are stored for inner matrices only");
     const DevSELL &S = *M.sell;
     launch_d16_spmv(M.nrows, count, S.streams(), S.val.p, x, y, alpha, beta, z, M.tag, nullptr, M.ncols, c.d16_unroll,
-                    c.st, slist, nullptr, lds_reserve, qout ? D16_AUX_STORE : D16_AUX_NONE, qout);
+                    c.d16_xcd, c.st, slist, nullptr, lds_reserve, qout ? D16_AUX_STORE : D16_AUX_NONE, qout);
 }
 
 void spmv_store_sums(const DevCSR &M, const double *x, double *y, Ctx &c, double alpha, double beta, const double *z,
@@ -714,7 +714,7 @@ void spmv_store_sums(const DevCSR &M, const double *x, double *y, Ctx &c, double
     if (!plain_d16(M) || M.tag) throw Error("spmv_store_sums: plain D16 layouts of inner matrices only");
     const DevSELL &S = *M.sell;
     launch_d16_spmv(M.nrows, S.nslices, S.streams(), S.val.p, x, y, alpha, beta, z, 0, nullptr, M.ncols, c.d16_unroll,
-                    c.st, nullptr, nullptr, 0, D16_AUX_STORE, qout);
+                    c.d16_xcd, c.st, nullptr, nullptr, 0, D16_AUX_STORE, qout);
 }
 
 // ======================================================= coupling reuse ===
@@ -904,10 +904,10 @@ void MatOp::product_after(const PC &pc, const double *x, double *y, Ctx &c, bool
     if (timers) timers->begin(T_SPMV);
     if (lo)
         launch_d16_spmv(M->nrows, S.nslices, S.streams(), S.val32.p, x, y, 1.0, 0.0, nullptr, 1, nullptr, M->ncols,
-                        c.d16_unroll_single, c.st, nullptr, nullptr, 0, R->q.p);
+                        c.d16_unroll_single, c.d16_xcd, c.st, nullptr, nullptr, 0, R->q.p);
     else
         launch_d16_spmv(M->nrows, S.nslices, S.streams(), S.val.p, x, y, 1.0, 0.0, nullptr, 1, nullptr, M->ncols,
-                        c.d16_unroll, c.st, nullptr, nullptr, 0, D16_AUX_INIT, R->q.p);
+                        c.d16_unroll, c.d16_xcd, c.st, nullptr, nullptr, 0, D16_AUX_INIT, R->q.p);
     if (timers) {
         timers->end(T_SPMV);
         timers->spmv_calls++;
@@ -1290,6 +1290,7 @@ std::unique_ptr<Ctx> layout_ctx(const Ctx &c) {
     self->sell_d16 = c.sell_d16;
     self->d16_wide_lpr = c.d16_wide_lpr;
     self->d16_unroll = c.d16_unroll;
+    self->d16_xcd = c.d16_xcd;
     self->d16_unroll_single = c.d16_unroll_single;
     self->d16_segs = c.d16_segs;
     self->d16_sigma = c.d16_sigma;

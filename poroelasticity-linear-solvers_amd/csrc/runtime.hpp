@@ -75,6 +75,7 @@ struct Ctx {
     bool sell_d16 = true;     // build SpMV layouts as SELL-64/D16 where every row fits
     int d16_wide_lpr = 8;     // lanes per row of D16 slices with wide rows (option pls.d16_wide_lpr)
     int d16_unroll = 4;       // D16 SpMV 8-entry groups per lane in flight (option pls.d16_unroll)
+    int d16_xcd = 0;          // D16 SpMV workgroup -> slice order: 1 XCD-contiguous ranges (option pls.d16_xcd)
     int d16_unroll_single = 8;  // ... of the fp32-value kernel: 1, 2, 4 or 8 (option pls.d16_unroll_single)
     int d16_segs = D16_SEG;   // minimum D16 segment bases per lane (option pls.d16_segs; 8 where needed)
     int d16_sigma = 1024;         // SELL-C-sigma window (rows sorted by length; 0: never) (pls.d16_sigma)

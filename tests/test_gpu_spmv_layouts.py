@@ -107,10 +107,40 @@ def test_unroll_does_not_change_the_sums(gpu, name):
 def test_xcd_block_map_gives_the_same_bits(gpu, name):
     """pls.d16_xcd 1 hands every XCD a contiguous range of slices; the grid is rounded up to a
     multiple of 8 blocks and the surplus blocks exit.  Same bits as pls.d16_xcd 0 before and after
-    in this process: the flag is process-wide and the next handle puts it back."""
+    in this process: the flag is an option of the handle, one handle at a time here."""
     case = C.BY_ID[name]
     runs = [(_check_exact(case, {"pls.d16_xcd": v}), _check_rounded(case, {"pls.d16_xcd": v}))
             for v in ("0", "1", "0")]
     for yi, yr in runs[1:]:
         assert np.array_equal(yi, runs[0][0])
         assert np.array_equal(yr, runs[0][1])
+
+
+@pytest.mark.parametrize("name", C.XCD_CASES)
+def test_xcd_flag_belongs_to_the_handle(gpu, name):
+    """Two handles on one matrix, pls.d16_xcd 1 and 0, both alive, multiplied in the order 1, 0, 1,
+    0: every product of the "int" data equals the int64 product bit for bit.  One value of the
+    handle decides both the grid rounding and the kernel's block map.  These cases' slice counts are
+    no multiple of 32 (tests/test_spmv_layout_restatement.py), so the rounded grid has surplus
+    blocks, and a map under an unrounded grid -- one handle's flag reaching another's launch --
+    would skip slices.  The mapped and the plain product are bitwise equal by design, so this
+    guards only a grid and a map that disagree; it cannot see which map ran."""
+    from lib.handle import Handle
+    case = C.BY_ID[name]
+    A, x = C.matrix(case, "int")
+    n = A.shape[0]
+    is_s, is_f, is_p, _ = C.index_sets(case, n)
+    exact = C.exact_product(A, x).astype(np.float64)
+    handles = []
+    try:
+        for v in ("1", "0"):
+            handles.append(Handle.from_csr(A, sp.identity(n, format="csr"), None, is_s, is_f, is_p, [],
+                                           dict(case.options, **{"pls.d16_xcd": v})))
+        for turn in range(4):
+            y = handles[turn % 2].matmult(x)
+            wrong = np.nonzero(y != exact)[0]
+            print(f"{case.id} product {turn} (pls.d16_xcd {1 - turn % 2}): rows wrong {len(wrong)}")
+            assert np.array_equal(y, exact)
+    finally:
+        for h in handles:
+            h.destroy()
