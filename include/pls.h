@@ -417,6 +417,14 @@ int pls_spmv_layout(pls_handle *h, int32_t *d16, int64_t *matrix_bytes);
  * bytes one low product streams, 4 B per stored entry for the values instead
  * of 8 (0 where d16 = 0).                                                    */
 int pls_spmv_layout_single(pls_handle *h, int32_t *d16, int64_t *matrix_bytes);
+/* Shared delta streams of a SELL-64/D16 layout (options pls.d16_share -1 auto /
+ * 0 never / 1 always, pls.d16_share_min_bytes): which = 0 A's layout, 1 the
+ * reduced outer layout of the coupling reuse (zeros while not eligible).
+ * stats[0] 1 when the layout's deltas are a shared stream, [1] its slices,
+ * [2] those with fewer than 64 classes, [3] the 16-bit deltas it stores
+ * (the padded entries when not shared), [4] layouts this handle has built
+ * with a shared stream so far (inner blocks included).                       */
+int pls_get_d16_share(pls_handle *h, int32_t which, int64_t stats[5]);
 /* Streaming probe on the current device: per repetition `bytes` read (and,
  * unless read_only, `bytes` written) with 16-B-per-lane nontemporal accesses;
  * returns GB/s of bytes moved -- the achievable HBM rate beside the 8 TB/s

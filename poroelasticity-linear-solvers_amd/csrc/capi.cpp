@@ -73,6 +73,9 @@ struct Handle {
             throw Error("pls.d16_wide_lpr must be a power of two <= 64");
         ctx.d16_unroll = (int)opt.integer("pls.d16_unroll", 4);
         ctx.d16_xcd = (int)opt.integer("pls.d16_xcd", 0);  // workgroup -> slice order (tuning)
+        ctx.d16_share = (int)opt.integer("pls.d16_share", -1);  // shared delta streams: -1 auto, 0 never, 1 always
+        if (ctx.d16_share < -1 || ctx.d16_share > 1) throw Error("pls.d16_share must be -1, 0 or 1");
+        ctx.d16_share_min_bytes = opt.integer("pls.d16_share_min_bytes", 268435456);
         ctx.d16_unroll_single = (int)opt.integer("pls.d16_unroll_single", 8);  // the fp32-value kernel's depth
         if (ctx.d16_unroll_single != 1 && ctx.d16_unroll_single != 2 && ctx.d16_unroll_single != 4 &&
             ctx.d16_unroll_single != 8)
@@ -1088,6 +1091,22 @@ int pls_spmv_layout_single(pls_handle *hh, int32_t *d16, int64_t *matrix_bytes) 
         const bool ok = H.A.sell && H.A.sell->d16 && !H.A.sell->b3_nslices;
         if (d16) *d16 = ok ? 1 : 0;
         if (matrix_bytes) *matrix_bytes = ok ? H.A.sell->bytes_low() : 0;
+    })
+}
+
+int pls_get_d16_share(pls_handle *hh, int32_t which, int64_t *stats) {
+    PLS_TRY({
+        Handle &H = *reinterpret_cast<Handle *>(hh);
+        if (!stats) throw Error("pls_get_d16_share: null argument");
+        if (which != 0 && which != 1) throw Error("pls_get_d16_share: which must be 0 (A) or 1 (the reduced outer layout)");
+        if (which == 0) build_sell(H.A, H.ctx);
+        const DevSELL *S = which == 0 ? H.A.sell.get() : H.coupling.eligible ? &H.coupling.reduced : nullptr;
+        const bool d16 = S && S->d16;
+        stats[0] = d16 && S->cls.p ? 1 : 0;
+        stats[1] = d16 ? S->nslices : 0;
+        stats[2] = d16 ? S->shared_slices : 0;
+        stats[3] = d16 ? S->dstored : 0;
+        stats[4] = H.ctx.d16_share_built;
     })
 }
 

@@ -1743,6 +1743,85 @@ __global__ __launch_bounds__(TPB) void k_d16_fill(int64_t nslices, const int64_t
     for (int j = nseg; j < nsegs; ++j) seg[slot * nsegs + j] = seg[slot * nsegs + nseg - 1];
 }
 
+// ---- shared delta streams (pls.d16_share) ----
+// Lanes of a slice whose delta streams are equal over the slice's whole length (padding
+// included) form a class; the shared stream stores one 16-B pack per class and 8-entry group,
+//   deltas  dls[dptr[slice] + (g * C + cls[slice * 64 + lane]) * 8 + k % 8]   (g = k / 8)
+// C = classes of the slice, ids ordered by lowest member lane.  C = 64 with cls = lane is the
+// plain stream.  Both kernels read the plain stream k_d16_fill wrote (rowmap and rstart are in
+// it already), one wave per slice.
+typedef uint32_t d16_u4 __attribute__((ext_vector_type(4)));
+
+// lowest lane whose 64-bit key equals this lane's
+__device__ __forceinline__ int d16_lowest_equal(uint64_t key, int lane) {
+    int rep = lane;
+    for (int j = 63; j >= 0; --j) {
+        const uint64_t kj = __shfl(key, j);
+        if (kj == key) rep = j;
+    }
+    return rep;
+}
+
+// cls[slice * 64 + lane] and cnt[slice] = C * L (the slice's stored deltas); *nshared counts
+// the slices with C < 64.  Each lane hashes its stream, takes the lowest lane with the same
+// hash as representative and compares its stream with the representative's pack by pack; one
+// mismatch anywhere in the slice (a hash collision) and the slice keeps C = 64.
+__global__ __launch_bounds__(TPB) void k_d16_share_classes(int64_t nslices, const int64_t *__restrict__ sptr,
+                                                           const uint16_t *__restrict__ dl, uint8_t *cls,
+                                                           int64_t *cnt, int64_t *nshared) {
+    const int64_t sl = ((int64_t)blockIdx.x * TPB + threadIdx.x) >> 6;
+    const int lane = threadIdx.x & 63;
+    if (sl > nslices) return;
+    if (sl == nslices) { if (lane == 0) cnt[nslices] = 0; return; }
+    const int64_t base = sptr[sl];
+    const int64_t L = (sptr[sl + 1] - base) >> 6;
+    const int64_t ng = L >> 3;
+    const d16_u4 *dp = reinterpret_cast<const d16_u4 *>(dl + base);
+    uint64_t h = 0xcbf29ce484222325ull;
+    for (int64_t g = 0; g < ng; ++g) {
+        const d16_u4 d = dp[g * 64 + lane];
+        h = (h ^ (((uint64_t)d.y << 32) | d.x)) * 0x9e3779b97f4a7c15ull;
+        h ^= h >> 29;
+        h = (h ^ (((uint64_t)d.w << 32) | d.z)) * 0xbf58476d1ce4e5b9ull;
+        h ^= h >> 32;
+    }
+    const int rep = d16_lowest_equal(h, lane);
+    bool same = true;
+    if (rep != lane)
+        for (int64_t g = 0; g < ng && same; ++g) {
+            const d16_u4 a = dp[g * 64 + lane], b = dp[g * 64 + rep];
+            same = a.x == b.x && a.y == b.y && a.z == b.z && a.w == b.w;
+        }
+    const bool ok = !__any(!same);
+    const uint64_t reps = ok ? __ballot(rep == lane) : ~0ull;
+    const int c = ok ? __popcll(reps & ((1ull << rep) - 1ull)) : lane;
+    const int C = __popcll(reps);
+    cls[sl * 64 + lane] = (uint8_t)c;
+    if (lane == 0) {
+        cnt[sl] = C * L;
+        if (C < 64) atomicAdd(reinterpret_cast<unsigned long long *>(nshared), 1ull);
+    }
+}
+
+// the shared stream from the plain one: the lowest lane of every class copies its packs
+__global__ __launch_bounds__(TPB) void k_d16_share_fill(int64_t nslices, const int64_t *__restrict__ sptr,
+                                                        const int64_t *__restrict__ dptr,
+                                                        const uint8_t *__restrict__ cls,
+                                                        const uint16_t *__restrict__ dl, uint16_t *dls) {
+    const int64_t sl = ((int64_t)blockIdx.x * TPB + threadIdx.x) >> 6;
+    const int lane = threadIdx.x & 63;
+    if (sl >= nslices) return;
+    const int64_t base = sptr[sl];
+    const int64_t ng = (sptr[sl + 1] - base) >> 9;
+    const int c = cls[sl * 64 + lane];
+    const bool first = d16_lowest_equal((uint64_t)c, lane) == lane;
+    const int C = __popcll(__ballot(first));
+    if (!first) return;
+    const d16_u4 *src = reinterpret_cast<const d16_u4 *>(dl + base) + lane;
+    d16_u4 *dst = reinterpret_cast<d16_u4 *>(dls + dptr[sl]) + c;
+    for (int64_t g = 0; g < ng; ++g) dst[g * C] = src[g * 64];
+}
+
 // first column of every row (-1: empty row) -- input of the host slice plan
 __global__ __launch_bounds__(TPB) void k_first_col(int64_t nrows, const int64_t *rp, const int32_t *ci, int32_t *c0) {
     const int64_t r = (int64_t)blockIdx.x * TPB + threadIdx.x;
@@ -1750,7 +1829,6 @@ __global__ __launch_bounds__(TPB) void k_first_col(int64_t nrows, const int64_t 
 }
 
 typedef int32_t d16_i4 __attribute__((ext_vector_type(4)));
-typedef uint32_t d16_u4 __attribute__((ext_vector_type(4)));
 typedef double d16_d2 __attribute__((ext_vector_type(2)));
 typedef float d16_f4 __attribute__((ext_vector_type(4)));
 
@@ -1785,8 +1863,10 @@ struct d16_values<float> {
 //   D16_AUX_INIT   acc starts from aux[row] instead of 0
 // V: the value stream's type (d16_values); x, every product (double)a * x[col] and every sum are
 // fp64 and in the same order for both.
+// (the second launch bound: the unroll-8 halo instantiations stay at 128 VGPRs, 4 waves per SIMD,
+// as before the class addressing; without it the allocator takes 138)
 template <int G2, int TAG, bool HALO, int SEG, int AUX, class V>
-__global__ __launch_bounds__(TPB) void k_d16_spmv(int64_t nrows, int64_t nslices, const int64_t *__restrict__ sptr,
+__global__ __launch_bounds__(TPB, (G2 == 8 && SEG == 4 && HALO) ? 4 : 1) void k_d16_spmv(int64_t nrows, int64_t nslices, const int64_t *__restrict__ sptr,
                                                   const int64_t *__restrict__ sfirst,
                                                   const int32_t *__restrict__ slpr,
                                                   const uint16_t *__restrict__ dl, const V *__restrict__ dv,
@@ -1794,7 +1874,9 @@ __global__ __launch_bounds__(TPB) void k_d16_spmv(int64_t nrows, int64_t nslices
                                                   double *__restrict__ y, double alpha, double beta,
                                                   const double *__restrict__ z, const double *__restrict__ ghost,
                                                   int32_t nlocal, const int32_t *__restrict__ slist,
-                                                  const int32_t *__restrict__ rowmap, double *aux, int d16_xcd) {
+                                                  const int32_t *__restrict__ rowmap, double *aux, int d16_xcd,
+                                                  const int64_t *__restrict__ dptr,
+                                                  const uint8_t *__restrict__ cls) {
     static_assert(SEG == 4 || SEG == 8, "segment bases are one or two int4 per lane");
     static_assert(AUX != D16_AUX_STORE || d16_values<V>::AUX_STORE, "the raw-sum store belongs to the fp64 launch");
     typedef typename d16_values<V>::pack pack;
@@ -1822,7 +1904,22 @@ __global__ __launch_bounds__(TPB) void k_d16_spmv(int64_t nrows, int64_t nslices
     const d16_i4 sb = __builtin_nontemporal_load(reinterpret_cast<const d16_i4 *>(seg) + (sl * 64 + lane) * (SEG / 4));
     d16_i4 sb2 = sb;
     if (SEG == 8) sb2 = __builtin_nontemporal_load(reinterpret_cast<const d16_i4 *>(seg) + (sl * 64 + lane) * 2 + 1);
-    const d16_u4 *dp = reinterpret_cast<const d16_u4 *>(dl + base) + lane;
+    // the delta packs of an 8-entry group lie gs packs apart: 64 (one per lane), or with a
+    // shared stream (cls, see k_d16_share_classes) one per class of the slice
+    int64_t dbase = base, gs = 64;
+    int dlane = lane;
+    if (cls) {
+        dlane = cls[sl * 64 + lane];
+        int C = dlane;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const int t = __shfl_xor(C, o);
+            C = t > C ? t : C;
+        }
+        gs = __builtin_amdgcn_readfirstlane(C) + 1;
+        dbase = dptr[sl];
+    }
+    const d16_u4 *dp = reinterpret_cast<const d16_u4 *>(dl + dbase) + dlane;
     const pack *vp = reinterpret_cast<const pack *>(dv + base) + lane;
     int32_t col = 0;
     int si = 0;
@@ -1835,7 +1932,7 @@ __global__ __launch_bounds__(TPB) void k_d16_spmv(int64_t nrows, int64_t nslices
 #pragma unroll
         for (int u = 0; u < G2; ++u) {
             const int64_t g = g0 + u < ng ? g0 + u : ng - 1;  // wave-uniform clamp, values masked
-            d[u] = __builtin_nontemporal_load(dp + g * 64);
+            d[u] = __builtin_nontemporal_load(dp + g * gs);
 #pragma unroll
             for (int q = 0; q < NQ; ++q) v[u][q] = __builtin_nontemporal_load(vp + (g * NQ + q) * 64);
         }
@@ -1896,6 +1993,15 @@ void launch_d16_fill(int64_t nslices, const int64_t *sfirst, const int32_t *slpr
         k_d16_fill<<<grid_for(nslices * 64, TPB), TPB, 0, st>>>(nslices, sfirst, slpr, rp, ci, val, nrows, sptr, dl,
                                                                 dv, seg, nsegs, rowmap, rstart);
 }
+void launch_d16_share_classes(int64_t nslices, const int64_t *sptr, const uint16_t *dl, uint8_t *cls, int64_t *cnt,
+                              int64_t *nshared, hipStream_t st) {
+    k_d16_share_classes<<<grid_for((nslices + 1) * 64, TPB), TPB, 0, st>>>(nslices, sptr, dl, cls, cnt, nshared);
+}
+void launch_d16_share_fill(int64_t nslices, const int64_t *sptr, const int64_t *dptr, const uint8_t *cls,
+                           const uint16_t *dl, uint16_t *dls, hipStream_t st) {
+    if (nslices > 0)
+        k_d16_share_fill<<<grid_for(nslices * 64, TPB), TPB, 0, st>>>(nslices, sptr, dptr, cls, dl, dls);
+}
 // see launch_coupling_rows (kernels.hpp); one thread per row
 __global__ __launch_bounds__(TPB) void k_coupling_rows(int64_t n, int64_t ns, const int64_t *rp, const int32_t *ci,
                                                        const double *val, const int64_t *mrp, const int32_t *mci,
@@ -1952,7 +2058,8 @@ template <int G2, int TAG, bool HALO, int SEG, int AUX, class V>
 static void d16_go(const D16Call<V> &a) {
     k_d16_spmv<G2, TAG, HALO, SEG, AUX, V><<<a.g, TPB, a.shm, a.st>>>(a.nrows, a.ns, a.L.sptr, a.L.sfirst, a.L.slpr,
                                                                       a.L.dl, a.dv, a.L.seg, a.x, a.y, a.alpha, a.beta,
-                                                                      a.z, a.ghost, a.nl, a.slist, a.rm, a.aux, a.d16_xcd);
+                                                                      a.z, a.ghost, a.nl, a.slist, a.rm, a.aux, a.d16_xcd,
+                                                                      a.L.dptr, a.L.cls);
 }
 // the raw-sum store serves the block PC's coupling launches (tag 0, fp64 values only), the
 // initial value the outer operator's reduced launch (tag 1); both on one rank only, plain

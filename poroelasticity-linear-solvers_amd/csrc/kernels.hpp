@@ -277,6 +277,13 @@ void launch_d16_fill(int64_t nslices, const int64_t *sfirst, const int32_t *slpr
                      const int32_t *ci, const double *val, int64_t nrows, const int64_t *sptr, uint16_t *dl,
                      double *dv, int32_t *seg, int nsegs /* D16_SEG or D16_SEG_MAX */, hipStream_t st,
                      const int32_t *rowmap = nullptr, const int64_t *rstart = nullptr);
+// Shared delta streams: the classes of every slice of a filled layout (cls: nslices * 64;
+// cnt: nslices + 1, stored deltas per slice, to be scanned into dptr; *nshared += slices with
+// fewer than 64 classes), then the shared stream dls from the plain one dl (kernels.hip)
+void launch_d16_share_classes(int64_t nslices, const int64_t *sptr, const uint16_t *dl, uint8_t *cls, int64_t *cnt,
+                              int64_t *nshared, hipStream_t st);
+void launch_d16_share_fill(int64_t nslices, const int64_t *sptr, const int64_t *dptr, const uint8_t *cls,
+                           const uint16_t *dl, uint16_t *dls, hipStream_t st);
 // The coupling block of the outer operator: rows [ns, n) x columns [0, ns) of A (sorted
 // columns) against the block M the preconditioner multiplies with.  rstart[r] = the first
 // entry of row r with a column >= ns where reuse[r], else rp[r]; *differs = 1 when a row's
@@ -294,6 +301,10 @@ struct D16Streams {
     const uint16_t *dl;
     const int32_t *seg;
     int nsegs;
+    // shared delta stream (pls.d16_share): dl is then addressed through dptr (nslices + 1) and
+    // cls (a class per lane); both null: one delta pack per lane at the value stream's offsets
+    const int64_t *dptr = nullptr;
+    const uint8_t *cls = nullptr;
 };
 void launch_d16_spmv(int64_t nrows, int64_t nslices, const D16Streams &L, const double *dv, const double *x, double *y,
                      double alpha, double beta, const double *z, int tag, const double *ghost, int64_t nlocal,

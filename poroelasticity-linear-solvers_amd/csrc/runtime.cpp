@@ -476,6 +476,37 @@ static bool build_sell_rcm(DevCSR &M, Ctx &c) {
     return true;
 }
 
+// Shared delta stream of a filled D16 layout (pls.d16_share; format: kernels.hip).  Auto (-1)
+// takes it where a product re-streams the matrix from memory -- the plain layout exceeds
+// pls.d16_share_min_bytes, the size of the last-level cache -- and the shared layout is
+// smaller; otherwise S stays as it is.  Only the totals come back to the host.
+static void d16_share(DevSELL &S, Ctx &c) {
+    const int64_t ns = S.nslices;
+    if (c.d16_share == 0 || ns == 0 || S.stored == 0) return;
+    if (c.d16_share < 0 && S.bytes() <= c.d16_share_min_bytes) return;
+    DBuf<uint8_t> cls(ns * 64);
+    DBuf<int64_t> cnt(ns + 1), dptr(ns + 1), nshared(1);
+    HIPCHK(hipMemsetAsync(nshared.p, 0, sizeof(int64_t), c.st));
+    launch_d16_share_classes(ns, S.sptr.p, S.dl.p, cls.p, cnt.p, nshared.p, c.st);
+    c.ensure_scan(ns);
+    exclusive_scan_i64(cnt.p, dptr.p, ns, c.scan_tmp.p, c.scan_tmp_bytes, c.st);
+    int64_t total = 0, shared = 0;
+    HIPCHK(hipMemcpyAsync(&total, dptr.p + ns, sizeof(int64_t), hipMemcpyDeviceToHost, c.st));
+    HIPCHK(hipMemcpyAsync(&shared, nshared.p, sizeof(int64_t), hipMemcpyDeviceToHost, c.st));
+    c.sync();
+    if (c.d16_share < 0 && total * 2 + ns * 72 + 8 >= S.stored * 2) return;  // nothing saved
+    DBuf<uint16_t> dls(std::max<int64_t>(total, 8));
+    launch_d16_share_fill(ns, S.sptr.p, dptr.p, cls.p, S.dl.p, dls.p, c.st);
+    HIPCHK(hipGetLastError());
+    c.sync();
+    S.dl = std::move(dls);  // (frees the plain stream)
+    S.dptr = std::move(dptr);
+    S.cls = std::move(cls);
+    S.dstored = total;
+    S.shared_slices = shared;
+    ++c.d16_share_built;
+}
+
 // The D16 arrays of M for a slice plan (sfirst, slpr, rowmap of d16_plan); rstart: see
 // launch_d16_fill.  False (S.d16 unset) when a lane needs more than D16_SEG_MAX segments.
 static bool d16_from_plan(const DevCSR &M, DevSELL &S, const std::vector<int64_t> &sf, const std::vector<int32_t> &lp,
@@ -516,6 +547,8 @@ static bool d16_from_plan(const DevCSR &M, DevSELL &S, const std::vector<int64_t
                     S.nsegs, c.st, rmap, rstart);
     HIPCHK(hipGetLastError());
     c.sync();
+    S.dstored = S.stored;
+    d16_share(S, c);
     return true;
 }
 
@@ -1291,6 +1324,8 @@ std::unique_ptr<Ctx> layout_ctx(const Ctx &c) {
     self->d16_wide_lpr = c.d16_wide_lpr;
     self->d16_unroll = c.d16_unroll;
     self->d16_xcd = c.d16_xcd;
+    self->d16_share = c.d16_share;
+    self->d16_share_min_bytes = c.d16_share_min_bytes;
     self->d16_unroll_single = c.d16_unroll_single;
     self->d16_segs = c.d16_segs;
     self->d16_sigma = c.d16_sigma;

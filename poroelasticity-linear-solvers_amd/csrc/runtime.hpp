@@ -76,6 +76,9 @@ struct Ctx {
     int d16_wide_lpr = 8;     // lanes per row of D16 slices with wide rows (option pls.d16_wide_lpr)
     int d16_unroll = 4;       // D16 SpMV 8-entry groups per lane in flight (option pls.d16_unroll)
     int d16_xcd = 0;          // D16 SpMV workgroup -> slice order: 1 XCD-contiguous ranges (option pls.d16_xcd)
+    int d16_share = -1;       // shared delta streams: -1 where they pay (see below), 0 never, 1 always (pls.d16_share)
+    int64_t d16_share_min_bytes = 268435456;  // ... -1: only layouts above this size (pls.d16_share_min_bytes)
+    int64_t d16_share_built = 0;              // D16 layouts built with a shared delta stream so far
     int d16_unroll_single = 8;  // ... of the fp32-value kernel: 1, 2, 4 or 8 (option pls.d16_unroll_single)
     int d16_segs = D16_SEG;   // minimum D16 segment bases per lane (option pls.d16_segs; 8 where needed)
     int d16_sigma = 1024;         // SELL-C-sigma window (rows sorted by length; 0: never) (pls.d16_sigma)
@@ -142,6 +145,12 @@ struct DevSELL {
     DBuf<int32_t> col;
     DBuf<double> val;
     DBuf<uint16_t> dl;
+    // shared delta stream (pls.d16_share; kernels.hip): dl holds one pack per class and 8-entry
+    // group, dstored deltas in all, addressed through dptr (nslices + 1) and cls (nslices * 64);
+    // both empty and dstored == stored: one pack per lane
+    DBuf<int64_t> dptr;
+    DBuf<uint8_t> cls;
+    int64_t dstored = 0, shared_slices = 0;  // stored deltas; slices with fewer than 64 classes
     DBuf<int32_t> seg, slpr;  // D16: segment bases per lane, lanes per row per slice
     DBuf<int64_t> sfirst;     // D16: first row of each slice (nslices + 1)
     int64_t wide_slices = 0;  // D16 slices with 8 lanes per row
@@ -167,12 +176,13 @@ struct DevSELL {
     // Compressed-operator GMRES (pls_gmres_operator single): the D16 values once more, rounded to
     // fp32, val32[base + (k / 4) * 256 + lane * 4 + k % 4] (build_low; empty until a KSP asks)
     DBuf<float> val32;
-    D16Streams streams() const { return {sptr.p, sfirst.p, slpr.p, dl.p, seg.p, nsegs}; }  // (D16 layouts)
+    D16Streams streams() const { return {sptr.p, sfirst.p, slpr.p, dl.p, seg.p, nsegs, dptr.p, cls.p}; }  // (D16 layouts)
     bool has_low() const { return d16 && !b3_nslices && val32.p != nullptr; }
     int64_t low_stream_bytes() const { return has_low() ? stored * 4 : 0; }
     int64_t bytes_low() const { return bytes() - stored * 4; }  // bytes one low product streams (D16 only)
     int64_t bytes() const {  // bytes one product streams from the matrix
-        return (d16 ? stored * 10 + nslices * (64 * 4 * nsegs + 20) + 8 + nrows_mapped * 4
+        return (d16 ? stored * 8 + dstored * 2 + (cls.p ? nslices * 72 + 8 : 0) + nslices * (64 * 4 * nsegs + 20) + 8 +
+                          nrows_mapped * 4
                     : stored * 12 + (nslices + 1) * 8) +
                b3_stored * 28 + b3_ntrip * 4 + (b3_nslices + 1) * 8 + nperm * 20;
     }

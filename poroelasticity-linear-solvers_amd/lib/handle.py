@@ -372,6 +372,14 @@ class Handle:
         N.check(N.lib().pls_get_reuse_stats(self.ptr, N.ptr(s)))
         return tuple(int(v) for v in s)
 
+    def d16_share(self, which=0):
+        """(shared 0/1, slices, slices with fewer than 64 classes, stored deltas, layouts this handle
+        built with a shared delta stream) of A's layout (which 0) or of the reduced outer layout
+        (which 1) (pls_get_d16_share)."""
+        s = np.zeros(5, dtype=np.int64)
+        N.check(N.lib().pls_get_d16_share(self.ptr, int(which), N.ptr(s)))
+        return tuple(int(v) for v in s)
+
     def reuse_rows(self):
         """uint8 mask, the caller's row order: 1 on the rows the reduced outer product starts from
         the block PC's raw sums; all 0 while the coupling reuse is not eligible (pls_get_reuse_rows)."""
