@@ -302,6 +302,12 @@ int pls_get_ksp_guess_info(pls_handle *h, const char *prefix, int64_t *reads_x, 
  * path is eligible for the next solve (decided when the solver is created and
  * again after pls_update_matrices), else 0.                                  */
 int pls_get_reuse_stats(pls_handle *h, int64_t stats[3]);
+/* The rows of the coupling reuse by kind (zeros while not eligible): stats[0]
+ * rows served by several lanes whose sums are continued lane by lane (option
+ * pls.reuse_wide: -1 wherever the reuse is eligible, 0 never), [1] their lanes
+ * per row, [2] the lane-per-row reuse rows, [3] the bytes one reduced outer
+ * product streams from its layout.                                           */
+int pls_get_reuse_wide(pls_handle *h, int64_t stats[4]);
 /* The rows of the coupling reuse: mask[i] = 1 (n bytes, the caller's row
  * order) where the reduced outer product starts row i from the block
  * preconditioner's raw sum, all 0 while the reduced path is not eligible.    */

@@ -69,7 +69,7 @@ void BlockPC::apply(const double *x, double *y, Ctx &c) {
             if (R) {
                 Timers::Span sp;
                 sp.a = T.mark(c.st);
-                spmv_store_sums(Mfp_s, y, t_fp.p, c, -1.0, 1.0, x + ns, R->q.p + ns);
+                spmv_store_sums(Mfp_s, y, t_fp.p, c, -1.0, 1.0, x + ns, R->q.p + ns, R->wide(ns));
                 sp.b = T.mark(c.st);
                 R->spans.push_back(sp);
             } else {
@@ -151,9 +151,10 @@ void BlockPC::apply_fp_pipeline(const double *x, double *y, Ctx &c) {
     // (coupling reuse: both launches store their raw row sums and are timed on their streams)
     Coupling *R = coupling && coupling->eligible ? coupling : nullptr;
     double *q = R ? R->q.p + ns : nullptr;
+    const D16Wide W = R ? R->wide(ns) : D16Wide();
     Timers::Span sp_hi, sp_lo;
     if (R) sp_hi.a = timers->mark(c.st);
-    spmv_slices(Mfp_s, y, t_fp.p, c, -1.0, 1.0, x + ns, F.sl_hi.p, F.n_hi, 0, q);
+    spmv_slices(Mfp_s, y, t_fp.p, c, -1.0, 1.0, x + ns, F.sl_hi.p, F.n_hi, 0, q, W);
     if (R) sp_hi.b = timers->mark(c.st);
     HIPCHK(hipEventRecord(F.ev_t, c.st));
     HIPCHK(hipStreamWaitEvent(c2.st, F.ev_t, 0));
@@ -162,7 +163,7 @@ void BlockPC::apply_fp_pipeline(const double *x, double *y, Ctx &c) {
     if (F.c_lo) HIPCHK(hipStreamWaitEvent(clo.st, F.ev_t, 0));
     // (pls.fp_pipeline_lds: its workgroups reserve LDS they do not use)
     if (R) sp_lo.a = timers->mark(clo.st);
-    spmv_slices(Mfp_s, y, t_fp.p, clo, -1.0, 1.0, x + ns, F.sl_lo.p, F.n_lo, F.lds, q);
+    spmv_slices(Mfp_s, y, t_fp.p, clo, -1.0, 1.0, x + ns, F.sl_lo.p, F.n_lo, F.lds, q, W);
     if (R) {
         sp_lo.b = timers->mark(clo.st);
         R->spans.push_back(sp_hi);

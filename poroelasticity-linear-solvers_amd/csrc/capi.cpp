@@ -76,6 +76,8 @@ struct Handle {
         ctx.d16_share = (int)opt.integer("pls.d16_share", -1);  // shared delta streams: -1 auto, 0 never, 1 always
         if (ctx.d16_share < -1 || ctx.d16_share > 1) throw Error("pls.d16_share must be -1, 0 or 1");
         ctx.d16_share_min_bytes = opt.integer("pls.d16_share_min_bytes", 268435456);
+        ctx.reuse_wide = (int)opt.integer("pls.reuse_wide", -1);  // coupling reuse on multi-lane rows: -1 auto, 0 off
+        if (ctx.reuse_wide != -1 && ctx.reuse_wide != 0) throw Error("pls.reuse_wide must be -1 (auto) or 0");
         ctx.d16_unroll_single = (int)opt.integer("pls.d16_unroll_single", 8);  // the fp32-value kernel's depth
         if (ctx.d16_unroll_single != 1 && ctx.d16_unroll_single != 2 && ctx.d16_unroll_single != 4 &&
             ctx.d16_unroll_single != 8)
@@ -258,6 +260,8 @@ static void decide_coupling(Handle &H) {
     else if (!build_coupling(H.A, H.ns, *H.bpc.coupling_block(), R, H.ctx)) why = R.why;
     if (!R.eligible) {
         R.reduced = DevSELL();
+        R.qw.release();
+        R.wide_rows = 0;
         R.why = why;
         if (mode == 1) throw Error("pls.reuse_coupling 1: the coupling product cannot be reused: " + why);
     }
@@ -848,6 +852,17 @@ int pls_get_reuse_stats(pls_handle *hh, int64_t *stats) {
         stats[0] = H.coupling.n_reduced;
         stats[1] = H.coupling.n_full;
         stats[2] = H.coupling.eligible ? 1 : 0;
+    })
+}
+int pls_get_reuse_wide(pls_handle *hh, int64_t *stats) {
+    PLS_TRY({
+        Handle &H = *reinterpret_cast<Handle *>(hh);
+        if (!stats) throw Error("pls_get_reuse_wide: null argument");
+        const Coupling &R = H.coupling;
+        stats[0] = R.eligible ? R.wide_rows : 0;
+        stats[1] = R.eligible && R.wide_rows ? R.wlpr : 0;
+        stats[2] = R.eligible ? R.reuse_rows : 0;
+        stats[3] = R.eligible ? R.reduced.bytes() : 0;
     })
 }
 

@@ -1660,6 +1660,17 @@ __device__ __forceinline__ void d16_lane(int64_t sl, int lane, const int64_t *sf
     else if (rowmap) row = rowmap[row];
 }
 
+// Rows of a reduced layout (rstart): a row served by lpr lanes keeps every remaining entry on
+// the lane it has in the full row.  The row lost m = rstart[row] - rp[row] leading entries, so
+// with phase = m % lpr lane `sub` takes the remaining entries j' = 0, 1, ... with
+// (j' + phase) % lpr == sub: the first at (sub - phase) mod lpr, then every lpr-th.  Phase 0
+// (no rstart, nothing skipped, lane-per-row) is the plain rule j' % lpr == sub.
+__device__ __forceinline__ int d16_first(int64_t row, int lpr, int sub, const int64_t *rp, const int64_t *rstart) {
+    if (!rstart || row < 0 || lpr == 1) return sub;
+    const int phase = (int)((rstart[row] - rp[row]) % lpr);
+    return (sub - phase + lpr) % lpr;
+}
+
 __global__ __launch_bounds__(TPB) void k_d16_slice_len(int64_t nslices, const int64_t *sfirst, const int32_t *slpr,
                                                        const int64_t *rp, int64_t nrows, int64_t *slen,
                                                        const int32_t *rowmap, const int64_t *rstart) {
@@ -1671,7 +1682,8 @@ __global__ __launch_bounds__(TPB) void k_d16_slice_len(int64_t nslices, const in
     int lpr, sub;
     d16_lane(sl, lane, sfirst, slpr, nrows, row, lpr, sub, rowmap);
     const int64_t len = row >= 0 ? rp[row + 1] - (rstart ? rstart[row] : rp[row]) : 0;
-    int64_t mine = len > sub ? (len - sub + lpr - 1) / lpr : 0;
+    const int first = d16_first(row, lpr, sub, rp, rstart);
+    int64_t mine = len > first ? (len - first + lpr - 1) / lpr : 0;
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
         const int64_t t = __shfl_xor(mine, o);
@@ -1695,7 +1707,7 @@ __global__ __launch_bounds__(TPB) void k_d16_count(int64_t nslices, const int64_
     const int64_t s = rstart ? rstart[row] : rp[row], e = rp[row + 1];
     int nseg = 0;
     int64_t last = -1;
-    for (int64_t k = s + sub; k < e; k += lpr) {
+    for (int64_t k = s + d16_first(row, lpr, sub, rp, rstart); k < e; k += lpr) {
         const int64_t c = ci[k];
         if (last < 0 || c - last > 65535 || c <= last) ++nseg;
         last = c;
@@ -1719,10 +1731,11 @@ __global__ __launch_bounds__(TPB) void k_d16_fill(int64_t nslices, const int64_t
     const int64_t s0 = row >= 0 ? (rstart ? rstart[row] : rp[row]) : 0;
     const int64_t len = row >= 0 ? rp[row + 1] - s0 : 0;
     const int64_t slot = sl * 64 + lane;
+    const int first = d16_first(row, lpr, sub, rp, rstart);
     int nseg = 0;
     int32_t last = 0;
     for (int64_t k = 0; k < L; ++k) {
-        const int64_t j = k * lpr + sub;  // this lane's k-th entry of the row
+        const int64_t j = k * lpr + first;  // this lane's k-th entry of the row
         uint16_t d = 0;
         double v = 0.0;
         if (j < len) {
@@ -1856,11 +1869,15 @@ struct d16_values<float> {
     }
 };
 
-// AUX (lane-per-row slices only; a lane's row sum is one chain acc += a * x[col] in CSR
-// order, so a chain stopped after a row's first columns and continued from the stored value
-// gives the bits of the unbroken one):
+// AUX (a lane's sum is one chain acc += a * x[col] over its entries in CSR order, so a chain
+// stopped after a row's first columns and continued from the stored value gives the bits of the
+// unbroken one):
 //   D16_AUX_STORE  aux[row] = acc, the raw row sum before alpha / beta
 //   D16_AUX_INIT   acc starts from aux[row] instead of 0
+// on lane-per-row slices.  Slices of W.lpr > 1 lanes per row do the same per lane, before the
+// shuffle combine, for the rows [W.lo, W.hi) through W.q[(row - W.lo) * W.lpr + lane % W.lpr]
+// (D16Wide; lpr 0: no such rows).  The lanes' entries must be the same in the storing and in
+// the continuing layout: d16_first's phase rule.
 // V: the value stream's type (d16_values); x, every product (double)a * x[col] and every sum are
 // fp64 and in the same order for both.
 // (the second launch bound: the unroll-8 halo instantiations stay at 128 VGPRs, 4 waves per SIMD,
@@ -1876,7 +1893,7 @@ __global__ __launch_bounds__(TPB, (G2 == 8 && SEG == 4 && HALO) ? 4 : 1) void k_
                                                   int32_t nlocal, const int32_t *__restrict__ slist,
                                                   const int32_t *__restrict__ rowmap, double *aux, int d16_xcd,
                                                   const int64_t *__restrict__ dptr,
-                                                  const uint8_t *__restrict__ cls) {
+                                                  const uint8_t *__restrict__ cls, D16Wide W) {
     static_assert(SEG == 4 || SEG == 8, "segment bases are one or two int4 per lane");
     static_assert(AUX != D16_AUX_STORE || d16_values<V>::AUX_STORE, "the raw-sum store belongs to the fp64 launch");
     typedef typename d16_values<V>::pack pack;
@@ -1924,7 +1941,10 @@ __global__ __launch_bounds__(TPB, (G2 == 8 && SEG == 4 && HALO) ? 4 : 1) void k_
     int32_t col = 0;
     int si = 0;
     double acc = 0.0;
+    // (wave-uniform but for the row bounds: a slice is lane-per-row or W.lpr lanes per row)
+    const bool wide = AUX != D16_AUX_NONE && lpr > 1 && lpr == W.lpr && row < r1 && row >= W.lo && row < W.hi;
     if (AUX == D16_AUX_INIT && lpr == 1 && row < r1) acc = aux[row];
+    if (AUX == D16_AUX_INIT && wide) acc = W.q[(row - W.lo) * lpr + lane % lpr];
     const int64_t ng = L >> 3;
     for (int64_t g0 = 0; g0 < ng; g0 += G2) {
         d16_u4 d[G2];
@@ -1958,6 +1978,7 @@ __global__ __launch_bounds__(TPB, (G2 == 8 && SEG == 4 && HALO) ? 4 : 1) void k_
             }
         }
     }
+    if (AUX == D16_AUX_STORE && wide) W.q[(row - W.lo) * lpr + lane % lpr] = acc;
     if (lpr > 1) {  // wave-uniform: combine the LPR partial sums of a row
         for (int o = 1; o < lpr; o <<= 1) acc += __shfl_xor(acc, o);
         if (lane % lpr) return;
@@ -2053,13 +2074,14 @@ struct D16Call {
     const int32_t *slist, *rm;
     double *aux;
     int d16_xcd;
+    D16Wide W;
 };
 template <int G2, int TAG, bool HALO, int SEG, int AUX, class V>
 static void d16_go(const D16Call<V> &a) {
     k_d16_spmv<G2, TAG, HALO, SEG, AUX, V><<<a.g, TPB, a.shm, a.st>>>(a.nrows, a.ns, a.L.sptr, a.L.sfirst, a.L.slpr,
                                                                       a.L.dl, a.dv, a.L.seg, a.x, a.y, a.alpha, a.beta,
                                                                       a.z, a.ghost, a.nl, a.slist, a.rm, a.aux, a.d16_xcd,
-                                                                      a.L.dptr, a.L.cls);
+                                                                      a.L.dptr, a.L.cls, a.W);
 }
 // the raw-sum store serves the block PC's coupling launches (tag 0, fp64 values only), the
 // initial value the outer operator's reduced launch (tag 1); both on one rank only, plain
@@ -2091,18 +2113,19 @@ template <class V>
 static void d16_launch(int64_t nrows, int64_t nslices, const D16Streams &L, const V *dv, const double *x, double *y,
                        double alpha, double beta, const double *z, int tag, const double *ghost, int64_t nlocal,
                        int unroll, int d16_xcd, hipStream_t st, const int32_t *slist, const int32_t *rowmap,
-                       size_t lds_reserve, int aux_mode, double *aux) {
+                       size_t lds_reserve, int aux_mode, double *aux, const D16Wide &W) {
     if (nslices <= 0) return;
     unsigned g = grid_for(nslices, TPB / 64);
     if (d16_xcd) g = (g + 7) / 8 * 8;  // every XCD range the same length (surplus blocks exit)
     D16Call<V> a{g, lds_reserve, st, nrows, nslices, L, dv, x, y, alpha, beta, z, ghost, (int32_t)nlocal, slist,
-                 rowmap, aux, d16_xcd};
+                 rowmap, aux, d16_xcd, W};
     if (aux_mode != D16_AUX_NONE) {
         a.ghost = nullptr;
         a.nl = 0;
         a.rm = nullptr;
     } else {
         a.aux = nullptr;
+        a.W = D16Wide();
     }
     if (L.nsegs == 8) d16_unrolled<8>(unroll, a, tag, aux_mode);
     else d16_unrolled<4>(unroll, a, tag, aux_mode);
@@ -2110,16 +2133,16 @@ static void d16_launch(int64_t nrows, int64_t nslices, const D16Streams &L, cons
 void launch_d16_spmv(int64_t nrows, int64_t nslices, const D16Streams &L, const double *dv, const double *x, double *y,
                      double alpha, double beta, const double *z, int tag, const double *ghost, int64_t nlocal,
                      int unroll, int d16_xcd, hipStream_t st, const int32_t *slist, const int32_t *rowmap,
-                     size_t lds_reserve, int aux_mode, double *aux) {
+                     size_t lds_reserve, int aux_mode, double *aux, const D16Wide &W) {
     d16_launch(nrows, nslices, L, dv, x, y, alpha, beta, z, tag, ghost, nlocal, unroll, d16_xcd, st, slist, rowmap,
-               lds_reserve, aux_mode, aux);
+               lds_reserve, aux_mode, aux, W);
 }
 void launch_d16_spmv(int64_t nrows, int64_t nslices, const D16Streams &L, const float *dv32, const double *x, double *y,
                      double alpha, double beta, const double *z, int tag, const double *ghost, int64_t nlocal,
                      int unroll, int d16_xcd, hipStream_t st, const int32_t *slist, const int32_t *rowmap,
-                     size_t lds_reserve, const double *aux_init) {
+                     size_t lds_reserve, const double *aux_init, const D16Wide &W) {
     d16_launch(nrows, nslices, L, dv32, x, y, alpha, beta, z, tag, ghost, nlocal, unroll, d16_xcd, st, slist, rowmap,
-               lds_reserve, aux_init ? D16_AUX_INIT : D16_AUX_NONE, const_cast<double *>(aux_init));
+               lds_reserve, aux_init ? D16_AUX_INIT : D16_AUX_NONE, const_cast<double *>(aux_init), W);
 }
 
 // ------------------------------------------- D16 with fp32 values (low) ---

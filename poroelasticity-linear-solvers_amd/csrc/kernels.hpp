@@ -265,7 +265,10 @@ void launch_sell_spmv(int64_t nrows, const int64_t *sptr, const int32_t *scol, c
 constexpr int D16_SEG = 4;      // segment bases per lane (rows of a single rank)
 constexpr int D16_SEG_MAX = 8;  // ... with halo columns (own s/f/p + a neighbour's s/f/p)
 // rstart (all three): where each row's entries begin inside [rp[row], rp[row + 1]) -- a layout
-// without the rows' first columns (the reduced outer operator); null: rp[row]
+// without the rows' first columns (the reduced outer operator); null: rp[row].  A row of
+// lpr > 1 lanes keeps each remaining entry on the lane it has in the full row: the phase
+// (rstart[row] - rp[row]) % lpr shifts the lanes (d16_first, kernels.hip); phase 0 is the
+// layout without rstart
 void launch_d16_slice_len(int64_t nslices, const int64_t *sfirst, const int32_t *slpr, const int64_t *rp,
                           int64_t nrows, int64_t *slen /* nslices+1 */, hipStream_t st,
                           const int32_t *rowmap = nullptr /* slice position -> row (SELL-C-sigma) */,
@@ -293,6 +296,14 @@ void launch_coupling_rows(int64_t n, int64_t ns, const int64_t *rp, const int32_
                           int64_t *rstart, int32_t *differs, hipStream_t st);
 // raw row sums of lane-per-row slices (launch_d16_spmv's aux): stored, or the initial value
 constexpr int D16_AUX_NONE = 0, D16_AUX_STORE = 1, D16_AUX_INIT = 2;
+// ... and the raw sums of the single lanes of rows served by lpr > 1 lanes, for the rows
+// [lo, hi) of the launch's layout: q[(row - lo) * lpr + lane of the row], stored or taken as
+// initial values with the same aux mode.  lpr 0: no such rows.
+struct D16Wide {
+    double *q = nullptr;
+    int64_t lo = 0, hi = 0;
+    int lpr = 0;
+};
 void launch_first_col(int64_t nrows, const int64_t *rp, const int32_t *ci, int32_t *c0, hipStream_t st);
 // the streams of a D16 layout that a launch reads beside the values (DevSELL::streams fills it)
 struct D16Streams {
@@ -316,7 +327,8 @@ void launch_d16_spmv(int64_t nrows, int64_t nslices, const D16Streams &L, const 
                      const int32_t *rowmap = nullptr /* slice position -> row (SELL-C-sigma) */,
                      size_t lds_reserve = 0 /* dynamic LDS per workgroup, unused: keeps the product's
                                                workgroups off CUs whose LDS a sweep holds */,
-                     int aux_mode = D16_AUX_NONE, double *aux = nullptr /* nrows: raw row sums, see D16_AUX_* */);
+                     int aux_mode = D16_AUX_NONE, double *aux = nullptr /* nrows: raw row sums, see D16_AUX_* */,
+                     const D16Wide &W = D16Wide());
 // Compressed-operator GMRES (pls_gmres_operator single): a D16 layout's values once more in fp32,
 // dv32[base + (k / 4) * 256 + lane * 4 + k % 4], rounded to nearest even from the fp64 stream
 // (stored: the layout's padded entries; *overflow = 1 when a finite value rounds to an infinity) ...
@@ -326,7 +338,8 @@ void launch_d16_round_values(int64_t stored, const double *dv, float *dv32, int3
 void launch_d16_spmv(int64_t nrows, int64_t nslices, const D16Streams &L, const float *dv32, const double *x, double *y,
                      double alpha, double beta, const double *z, int tag, const double *ghost, int64_t nlocal,
                      int unroll, int d16_xcd, hipStream_t st, const int32_t *slist = nullptr,
-                     const int32_t *rowmap = nullptr, size_t lds_reserve = 0, const double *aux_init = nullptr);
+                     const int32_t *rowmap = nullptr, size_t lds_reserve = 0, const double *aux_init = nullptr,
+                     const D16Wide &W = D16Wide());
 // SELL/B3: row triples sharing one column list (FE vector fields), see kernels.hip
 void launch_triple_flags(int64_t n, const int64_t *rp, const int32_t *ci, uint8_t *flag, hipStream_t st);
 int b3_lanes_per_triple();

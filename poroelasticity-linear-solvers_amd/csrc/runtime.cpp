@@ -734,20 +734,20 @@ bool plain_d16(const DevCSR &M) {
 }
 
 void spmv_slices(const DevCSR &M, const double *x, double *y, Ctx &c, double alpha, double beta, const double *z,
-                 const int32_t *slist, int64_t count, size_t lds_reserve, double *qout) {
+                 const int32_t *slist, int64_t count, size_t lds_reserve, double *qout, const D16Wide &W) {
     if (!plain_d16(M)) throw Error("spmv_slices: plain D16 layouts only");
     if (qout && M.tag) throw Error("spmv_slices: raw row sums are stored for inner matrices only");
     const DevSELL &S = *M.sell;
     launch_d16_spmv(M.nrows, count, S.streams(), S.val.p, x, y, alpha, beta, z, M.tag, nullptr, M.ncols, c.d16_unroll,
-                    c.d16_xcd, c.st, slist, nullptr, lds_reserve, qout ? D16_AUX_STORE : D16_AUX_NONE, qout);
+                    c.d16_xcd, c.st, slist, nullptr, lds_reserve, qout ? D16_AUX_STORE : D16_AUX_NONE, qout, W);
 }
 
 void spmv_store_sums(const DevCSR &M, const double *x, double *y, Ctx &c, double alpha, double beta, const double *z,
-                     double *qout) {
+                     double *qout, const D16Wide &W) {
     if (!plain_d16(M) || M.tag) throw Error("spmv_store_sums: plain D16 layouts of inner matrices only");
     const DevSELL &S = *M.sell;
     launch_d16_spmv(M.nrows, S.nslices, S.streams(), S.val.p, x, y, alpha, beta, z, 0, nullptr, M.ncols, c.d16_unroll,
-                    c.d16_xcd, c.st, nullptr, nullptr, 0, D16_AUX_STORE, qout);
+                    c.d16_xcd, c.st, nullptr, nullptr, 0, D16_AUX_STORE, qout, W);
 }
 
 // ======================================================= coupling reuse ===
@@ -756,6 +756,8 @@ bool build_coupling(const DevCSR &A, int64_t ns, const DevCSR &M, Coupling &R, C
     R.fresh_for = nullptr;
     R.reduced = DevSELL();
     R.reuse_rows = 0;
+    R.wide_rows = R.wlo = R.whi = 0;
+    R.wlpr = 0;
     R.reuse.clear();
     const int64_t n = A.nrows;
     if (!plain_d16(A) || !plain_d16(M)) {
@@ -766,7 +768,8 @@ bool build_coupling(const DevCSR &A, int64_t ns, const DevCSR &M, Coupling &R, C
         R.why = "the coupling block is not rows [ns, n) x columns [0, ns) of the outer operator";
         return false;
     }
-    // reuse rows: lane-per-row in A's plan and in M's
+    // reuse rows: lane-per-row in A's plan and in M's (1), and with pls.reuse_wide the rows that
+    // the same lpr > 1 lanes serve in both (2: their sums are kept per lane, Coupling::qw)
     const DevSELL &SA = *A.sell, &SM = *M.sell;
     std::vector<int64_t> sfa(SA.nslices + 1), sfm(SM.nslices + 1);
     std::vector<int32_t> lpa(SA.nslices), lpm(SM.nslices);
@@ -776,14 +779,34 @@ bool build_coupling(const DevCSR &A, int64_t ns, const DevCSR &M, Coupling &R, C
     HIPCHK(hipMemcpyAsync(lpm.data(), SM.slpr.p, sizeof(int32_t) * lpm.size(), hipMemcpyDeviceToHost, c.st));
     c.sync();
     std::vector<uint8_t> reuse(n, 0);
+    std::vector<int32_t> lanes(n, 0);  // lanes per row in M's plan (0: not an fp row)
     for (int64_t s = 0; s < SM.nslices; ++s)
-        if (lpm[s] == 1)
-            for (int64_t r = sfm[s]; r < std::min(sfm[s + 1], M.nrows); ++r) reuse[ns + r] = 1;
+        for (int64_t r = sfm[s]; r < std::min(sfm[s + 1], M.nrows); ++r) lanes[ns + r] = lpm[s];
+    bool wide_ok = c.reuse_wide != 0;
+    int64_t wlo = n, whi = 0;
     for (int64_t s = 0; s < SA.nslices; ++s)
         for (int64_t r = sfa[s]; r < std::min(sfa[s + 1], n); ++r) {
-            if (lpa[s] != 1) reuse[r] = 0;
-            R.reuse_rows += reuse[r];
+            if (lanes[r] == 1 && lpa[s] == 1) {
+                reuse[r] = 1;
+                R.reuse_rows++;
+            } else if (wide_ok && lanes[r] > 1 && lanes[r] == lpa[s]) {
+                if (R.wlpr == 0) R.wlpr = lpa[s];
+                if (lpa[s] != R.wlpr) {  // (plain plans know one wide lpr; qw is indexed with one)
+                    wide_ok = false;
+                    continue;
+                }
+                reuse[r] = 2;
+                wlo = std::min(wlo, r);
+                whi = std::max(whi, r + 1);
+                R.wide_rows++;
+            }
         }
+    if (!wide_ok && R.wide_rows > 0) {
+        for (uint8_t &f : reuse) f = f == 1;
+        R.wide_rows = 0;
+    }
+    if (R.wide_rows == 0) R.wlpr = 0;
+    else R.wlo = wlo, R.whi = whi;
     DBuf<uint8_t> dreuse(n);
     DBuf<int64_t> rstart(n);
     DBuf<int32_t> differs(1);
@@ -798,20 +821,28 @@ bool build_coupling(const DevCSR &A, int64_t ns, const DevCSR &M, Coupling &R, C
         R.why = "the preconditioner's coupling block differs from the outer operator's";
         return false;
     }
-    if (R.reuse_rows == 0) {
+    if (R.reuse_rows + R.wide_rows == 0) {
         R.why = "no row is lane-per-row in both layouts";
+        R.wide_rows = 0;
         return false;
     }
-    // A' on A's own slice plan: a reuse row stays lane-per-row whatever is left of it
+    // A' on A's own slice plan: a reuse row keeps its lanes per row whatever is left of it, and
+    // a wide one every remaining entry on the lane it has in A (the phase rule of k_d16_fill)
     if (!d16_from_plan(A, R.reduced, sfa, lpa, {}, rstart.p, c)) {
         R.why = "the reduced layout does not fit D16";
         R.reduced = DevSELL();
+        R.wide_rows = 0;
         return false;
     }
     if (R.q.n != (size_t)n) R.q.alloc(n);
     HIPCHK(hipMemsetAsync(R.q.p, 0, sizeof(double) * n, c.st));
+    const size_t nw = (size_t)((R.whi - R.wlo) * R.wlpr);
+    if (nw == 0) R.qw.release();
+    else if (R.qw.n != nw) R.qw.alloc(nw);
+    if (nw) HIPCHK(hipMemsetAsync(R.qw.p, 0, sizeof(double) * nw, c.st));
     c.sync();
     R.why.clear();
+    for (uint8_t &f : reuse) f = f != 0;
     R.reuse = std::move(reuse);
     R.eligible = true;
     return true;
@@ -937,10 +968,10 @@ void MatOp::product_after(const PC &pc, const double *x, double *y, Ctx &c, bool
     if (timers) timers->begin(T_SPMV);
     if (lo)
         launch_d16_spmv(M->nrows, S.nslices, S.streams(), S.val32.p, x, y, 1.0, 0.0, nullptr, 1, nullptr, M->ncols,
-                        c.d16_unroll_single, c.d16_xcd, c.st, nullptr, nullptr, 0, R->q.p);
+                        c.d16_unroll_single, c.d16_xcd, c.st, nullptr, nullptr, 0, R->q.p, R->wide(0));
     else
         launch_d16_spmv(M->nrows, S.nslices, S.streams(), S.val.p, x, y, 1.0, 0.0, nullptr, 1, nullptr, M->ncols,
-                        c.d16_unroll, c.d16_xcd, c.st, nullptr, nullptr, 0, D16_AUX_INIT, R->q.p);
+                        c.d16_unroll, c.d16_xcd, c.st, nullptr, nullptr, 0, D16_AUX_INIT, R->q.p, R->wide(0));
     if (timers) {
         timers->end(T_SPMV);
         timers->spmv_calls++;
@@ -1326,6 +1357,7 @@ std::unique_ptr<Ctx> layout_ctx(const Ctx &c) {
     self->d16_xcd = c.d16_xcd;
     self->d16_share = c.d16_share;
     self->d16_share_min_bytes = c.d16_share_min_bytes;
+    self->reuse_wide = c.reuse_wide;
     self->d16_unroll_single = c.d16_unroll_single;
     self->d16_segs = c.d16_segs;
     self->d16_sigma = c.d16_sigma;

@@ -79,6 +79,7 @@ struct Ctx {
     int d16_share = -1;       // shared delta streams: -1 where they pay (see below), 0 never, 1 always (pls.d16_share)
     int64_t d16_share_min_bytes = 268435456;  // ... -1: only layouts above this size (pls.d16_share_min_bytes)
     int64_t d16_share_built = 0;              // D16 layouts built with a shared delta stream so far
+    int reuse_wide = -1;      // coupling reuse on rows of several lanes: -1 wherever the reuse is eligible, 0 never (pls.reuse_wide)
     int d16_unroll_single = 8;  // ... of the fp32-value kernel: 1, 2, 4 or 8 (option pls.d16_unroll_single)
     int d16_segs = D16_SEG;   // minimum D16 segment bases per lane (option pls.d16_segs; 8 where needed)
     int d16_sigma = 1024;         // SELL-C-sigma window (rows sorted by length; 0: never) (pls.d16_sigma)
@@ -234,9 +235,10 @@ void build_low(DevSELL &S, Ctx &c, const std::string &who);
 // qout (plain D16 layouts): also qout[row] = the raw row sum, before alpha and beta, for the
 // rows of lane-per-row slices (launch_d16_spmv's D16_AUX_STORE)
 void spmv_slices(const DevCSR &M, const double *x, double *y, Ctx &c, double alpha, double beta, const double *z,
-                 const int32_t *slist, int64_t count, size_t lds_reserve = 0, double *qout = nullptr);
+                 const int32_t *slist, int64_t count, size_t lds_reserve = 0, double *qout = nullptr,
+                 const D16Wide &W = D16Wide());
 void spmv_store_sums(const DevCSR &M, const double *x, double *y, Ctx &c, double alpha, double beta, const double *z,
-                     double *qout);
+                     double *qout, const D16Wide &W = D16Wide());
 // true when M's layout is the plain D16 one (no halo, RCM relabelling, row triples or row map)
 bool plain_d16(const DevCSR &M);
 
@@ -345,6 +347,18 @@ struct Coupling {
     int64_t reuse_rows = 0;
     std::vector<uint8_t> reuse;  // per row (internal order): 1 on the reuse rows (empty: not eligible)
     DBuf<double> q;            // n: raw sums on the reuse rows; zero wherever the reduced launch reads it else
+    // Wide reuse rows: rows of wlpr > 1 lanes in A's plan and in M's (pls.reuse_wide).  qw holds
+    // the raw sum of every lane of the rows [wlo, whi) of A, (row - wlo) * wlpr + lane of the row;
+    // zeroed once: a lane without s-entries, and a row of the range that is wide in A only, read
+    // the zero.  wide(shift): the launch argument in the row numbering of A (0) or of M (ns).
+    DBuf<double> qw;
+    int64_t wide_rows = 0, wlo = 0, whi = 0;
+    int wlpr = 0;
+    D16Wide wide(int64_t shift) const {
+        D16Wide W;
+        if (eligible && wide_rows > 0) W = D16Wide{qw.p, wlo - shift, whi - shift, wlpr};
+        return W;
+    }
     const double *fresh_for = nullptr;  // the z the PC returned last, while q belongs to it
     std::vector<Timers::Span> spans;    // the PC's coupling launches of that application
     int64_t spans_flush = -1;

@@ -53,6 +53,7 @@ EXPORTS = [
     "pls_matmult_single", "pls_matmult_single_device", "pls_spmv_layout_single", "pls_bench_spmv_single",
     "pls_get_gmres_operator_stats", "pls_get_reuse_rows", "pls_get_asm_stats", "pls_get_asm_rows",
     "pls_get_bc_columns_stats", "pls_get_bc_columns_matrix", "pls_get_d16_share",
+    "pls_get_reuse_wide",
 ]
 
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p)
@@ -110,6 +111,7 @@ def lib():
     L.pls_get_bc_columns_stats.argtypes = [vp, C.c_char_p, vp]
     L.pls_get_bc_columns_matrix.argtypes = [vp, C.c_char_p, vp, vp, vp, vp]
     L.pls_get_reuse_stats.argtypes = [vp, vp]
+    L.pls_get_reuse_wide.argtypes = [vp, vp]
     L.pls_get_d16_share.argtypes = [vp, i32, vp]
     L.pls_hessenberg_eigenvalues.argtypes = [C.c_int, vp, C.c_int, vp, vp]
     L.pls_export_matrix.argtypes = [vp, C.c_int, C.POINTER(i64), C.POINTER(i64), vp, vp, vp]

@@ -372,6 +372,14 @@ class Handle:
         N.check(N.lib().pls_get_reuse_stats(self.ptr, N.ptr(s)))
         return tuple(int(v) for v in s)
 
+    def reuse_wide(self):
+        """(reuse rows served by several lanes, their lanes per row, lane-per-row reuse rows, bytes
+        one reduced outer product streams from its layout); zeros while the coupling reuse is not
+        eligible (pls_get_reuse_wide, option pls.reuse_wide)."""
+        s = np.zeros(4, dtype=np.int64)
+        N.check(N.lib().pls_get_reuse_wide(self.ptr, N.ptr(s)))
+        return tuple(int(v) for v in s)
+
     def d16_share(self, which=0):
         """(shared 0/1, slices, slices with fewer than 64 classes, stored deltas, layouts this handle
         built with a shared delta stream) of A's layout (which 0) or of the reduced outer layout
