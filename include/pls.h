@@ -134,7 +134,27 @@ int pls_set_device(int device);
  * over a fieldsplit: use fp_fieldsplit_{0,1}_), an operator that is not a
  * stored matrix (the Schur split), operator and preconditioner matrices that
  * differ, a sharded block.  pls_update_matrices detects and splits again.
- * pls_get_bc_columns_stats / pls_get_bc_columns_matrix report the split.     */
+ * pls_get_bc_columns_stats / pls_get_bc_columns_matrix report the split.
+ * BoomerAMG smoothers: "<prefix>pc_hypre_boomeramg_relax_type_all" takes
+ * symmetric-SOR/Jacobi (the default: hybrid symmetric Gauss-Seidel), Jacobi,
+ * l1scaled-Jacobi or Chebyshev; any other value is an error that lists the
+ * four.  On a level with operator A: Jacobi m_i = w / a_ii with w =
+ * "<prefix>pc_hypre_boomeramg_relax_weight_all" (default 1.0), l1scaled-Jacobi
+ * m_i = sign(a_ii) / sum_j |a_ij| (m_i = 1 where the denominator is zero); a
+ * sweep over a set I (all rows with no_CF, else C then F going down and F then
+ * C going up) is x += M_I (b - A x), grid_sweeps_all rounds of it.  Chebyshev
+ * ignores the C/F sets: each round is "<prefix>pls_boomeramg_chebyshev_order"
+ * (1-4, default 2) steps of the Jacobi-preconditioned Chebyshev recurrence on
+ * [f lmax, lmax], lmax = 1.1 x the power-iteration estimate of D^-1 A (15
+ * steps, rounded to fp32), f = "<prefix>pls_boomeramg_chebyshev_fraction" (in
+ * (0, 1), default 0.3).  Out-of-range values are errors that name the key; so
+ * is a sharded block with a type other than the default; the three keys are
+ * checked whatever the type.  Every step is one launch over a level whose
+ * layout is SELL-64/D16 without an RCM relabelling or a SELL/B3 part; other
+ * levels, and "pls.amg_relax_fused 0", run the residual and an elementwise
+ * step (the same bits).  The three need a symmetric block to
+ * keep CG's preconditioner symmetric ("<prefix>pls_bc_columns lift").
+ * pls_get_boomeramg_relax reports the smoother.                              */
 
 /* Build a solver from host CSR matrices in the caller's (e.g. dolfin
  * interleaved) ordering plus the field index sets (sorted global indices of
@@ -350,6 +370,25 @@ int pls_get_bc_columns_stats(pls_handle *h, const char *prefix, int64_t stats[5]
  * solves (field-major order).  Any pointer may be NULL.                       */
 int pls_get_bc_columns_matrix(pls_handle *h, const char *prefix, int32_t *bc_rows, int64_t *c_rp, int32_t *c_ci,
                               double *c_val);
+/* The smoother of the BoomerAMG stand-in (<prefix>pc_type hypre) of the KSP with
+ * this prefix: stats[0] the relax type, 0 symmetric-SOR/Jacobi, 1 Jacobi,
+ * 2 l1scaled-Jacobi, 3 Chebyshev, [1] the smoothed levels, [2] the Chebyshev
+ * order, [3] the levels whose steps are the fused launch, and for the most
+ * recent application [4] fused step launches, [5] elementwise step launches
+ * (the steps from a zero iterate, and those of the other levels).  lambda[l],
+ * l < cap: level l's eigenvalue estimate (0 for the other types and past the
+ * last level); may be NULL with cap 0.  Sets the preconditioner up if it was
+ * not yet.  An unknown prefix, or a PC that is not that AMG, is an error.     */
+int pls_get_boomeramg_relax(pls_handle *h, const char *prefix, int64_t stats[6], double *lambda, int32_t cap);
+/* One smoothing step of those relax types on the outer operator A, in the
+ * layout pls_matmult multiplies with (a diagnostic; host vectors of length n,
+ * the caller's order): x_new = x + dn, dn = a d + g (m (b - A x)), d = dn.
+ * d may be NULL: the a d term is then absent and nothing is stored.  fused 1
+ * asks for the single launch, which serves SELL-64/D16 layouts without an RCM
+ * relabelling or a SELL/B3 part; *was_fused says whether it ran, else the
+ * product and an elementwise step did.                                       */
+int pls_relax_step(pls_handle *h, const double *m, const double *b, const double *x, double *d, double a, double g,
+                   int32_t fused, double *x_new, int32_t *was_fused);
 /* Eigenvalues of the leading m x m part (1 <= m <= 64) of an upper Hessenberg
  * matrix stored by columns, H[i + j * ldh]; entries below the subdiagonal are
  * not read.  Host code (shifted QR, no LAPACK, no device): re[k] + i im[k], in

@@ -55,6 +55,10 @@ void concat_rows(HostCSR &C, std::vector<HostCSR> &part);
 HostCSR spgemm(const HostCSR &A, const HostCSR &B);
 // Ac = P^T (A P), bitwise spgemm(R, spgemm(A, P)); false when nc^2 doubles exceed max_bytes
 bool galerkin_fused(const HostCSR &A, const HostCSR &P, int64_t nc, double max_bytes, HostCSR &C);
+// 1 / a_ii per row, 1 where the diagonal is zero or not stored
+std::vector<double> jacobi_dinv(const HostCSR &A);
+// power iteration on D^-1 A from v = 1 (oracle power_lambda), rounded to float
+double power_lambda(const HostCSR &A, const std::vector<double> &dinv, int steps);
 // dense inverse by Gauss-Jordan with partial pivoting (coarsest level)
 HostCSR dense_inverse(const HostCSR &A);
 // SpMV layout for an AMG operator (SELL-64 for short rows, CSR otherwise)

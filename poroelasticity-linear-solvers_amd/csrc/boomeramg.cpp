@@ -21,6 +21,9 @@
 // chunk-block-diagonal part, i.e. one ILU-style apply of the factors
 // I + L D^-1 and D + U (PCILU in sgs mode) -- the chunks are its blocks, so
 // one workgroup sweeps each chunk on libpls's level-scheduled LDS sweeps.
+// relax_type_all Jacobi, l1scaled-Jacobi and Chebyshev (opt-in; the spec is
+// tests/boomeramg_relax_restatement.py) build no such
+// factors: a step is x_new = x + a d + g (m (b - A x)), one launch on D16 levels.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -1194,6 +1197,9 @@ struct BParams {
     int64_t coarsen_chunks = 1, coarsen_rows = 65536;  // HMIS partitions (pls.hypre_coarsen_*): 1 = none (np = 1, default), 0 = auto
     int paths = 1, K = 1;
     bool no_cf = false;
+    // relax_type_all: 0 symmetric-SOR/Jacobi (hybrid Gauss-Seidel), 1 Jacobi, 2 l1scaled-Jacobi, 3 Chebyshev
+    int relax = 0, cheb_order = 2;
+    double relax_weight = 1.0, cheb_fraction = 0.3;
     std::string ranks;  // pls.hypre_ranks: the level-0 rank partition ("G" or "n0,n1,..."), hypre under mpirun -np G
 };
 
@@ -1227,6 +1233,9 @@ std::vector<int64_t> part_starts(const std::vector<int64_t> &sizes) {
     return st;
 }
 
+// PETSc's names of hypre's relax types 6, 0, 18 and 16 (BParams::relax)
+const char *const RELAX_NAMES[4] = {"symmetric-SOR/Jacobi", "Jacobi", "l1scaled-Jacobi", "Chebyshev"};
+
 BParams parse_params(const Options &o, const std::string &prefix) {
     const std::string pre = prefix + "pc_hypre_boomeramg_";
     BParams p;
@@ -1249,8 +1258,19 @@ BParams parse_params(const Options &o, const std::string &prefix) {
     const std::string ct = o.str(pre + "coarsen_type", "HMIS"), it = o.str(pre + "interp_type", "ext+i");
     if (ct != "HMIS") throw Error(pre + "coarsen_type " + ct + ": only HMIS is implemented");
     if (it != "ext+i") throw Error(pre + "interp_type " + it + ": only ext+i is implemented");
-    const std::string rt = o.str(pre + "relax_type_all", "symmetric-SOR/Jacobi");
-    if (rt != "symmetric-SOR/Jacobi") throw Error(pre + "relax_type_all " + rt + ": only symmetric-SOR/Jacobi is implemented");
+    const std::string rt = o.str(pre + "relax_type_all", RELAX_NAMES[0]);
+    p.relax = -1;
+    for (int t = 0; t < 4; ++t)
+        if (rt == RELAX_NAMES[t]) p.relax = t;
+    if (p.relax < 0)
+        throw Error(pre + "relax_type_all " + rt + ": only symmetric-SOR/Jacobi, Jacobi, l1scaled-Jacobi and Chebyshev are implemented");
+    // read and checked whatever the type, as the restatement does
+    p.relax_weight = o.num(pre + "relax_weight_all", 1.0);
+    p.cheb_order = (int)o.integer(prefix + "pls_boomeramg_chebyshev_order", 2);
+    p.cheb_fraction = o.num(prefix + "pls_boomeramg_chebyshev_fraction", 0.3);
+    if (p.cheb_order < 1 || p.cheb_order > 4) throw Error(prefix + "pls_boomeramg_chebyshev_order must be 1, 2, 3 or 4");
+    if (!(p.cheb_fraction > 0.0 && p.cheb_fraction < 1.0))
+        throw Error(prefix + "pls_boomeramg_chebyshev_fraction must lie in (0, 1)");
     if (p.K < 1) throw Error(pre + "grid_sweeps_all must be >= 1");
     if (p.paths < 1) throw Error(pre + "agg_num_paths must be >= 1");
     return p;
@@ -1428,6 +1448,7 @@ struct RelaxSet {  // the points one Gauss-Seidel pass visits (all, C or F)
     DBuf<int64_t> idx;
     DevCSR sub;                // C / F sets: the chunk-block-diagonal part restricted to the set
     std::unique_ptr<PC> sgs;   // r -> M^-1 r: one hybrid symmetric GS sweep from 0
+    DBuf<double> mvec;         // Jacobi types: m_i on the set's rows, 0 elsewhere (all n rows of the level)
 };
 
 struct BLevel {
@@ -1440,10 +1461,16 @@ struct BLevel {
     // rows, set_global the sets' sizes over all ranks
     int64_t gn = 0;
     std::vector<int64_t> set_global;
+    // relax types Jacobi, l1scaled-Jacobi, Chebyshev: whether the level's layout takes the fused
+    // step (launch_d16_relax); Chebyshev's 1 / a_ii and eigenvalue estimate
+    bool fused = false;
+    DBuf<double> dinv;
+    double lam = 0.0;
 };
 
 struct BWork {
     std::vector<DBuf<double>> r, t, x, b, xs, rs, ts;
+    std::vector<DBuf<double>> d;  // Chebyshev: the recurrence's direction
     DBuf<double> cx, cb;
     DBuf<double> csend, cgath, cbg, cxg;  // sharded: the coarsest level's gather
 };
@@ -1460,6 +1487,13 @@ struct PCBoomer : PC {
     std::unique_ptr<PC> Clu;
     std::unique_ptr<DevCSR> Cmat;
     std::map<hipStream_t, std::unique_ptr<BWork>> work;
+    // relax_type_all (BParams::relax) and what the types other than 0 need: Chebyshev's order and
+    // lmin / lmax, whether D16 levels take the fused step (pls.amg_relax_fused), and the fused /
+    // unfused step launches of the last application (pls_get_boomeramg_relax)
+    int relax_type = 0, cheb_order = 2;
+    double cheb_fraction = 0.3;
+    bool relax_fused = true;
+    int64_t n_fused = 0, n_unfused = 0;
 
     bool reentrant() const override { return true; }
 
@@ -1468,7 +1502,7 @@ struct PCBoomer : PC {
         if (!w) {
             w = std::make_unique<BWork>();
             const size_t L = lv.size();
-            for (auto *v : {&w->r, &w->t, &w->x, &w->b, &w->xs, &w->rs, &w->ts}) v->resize(L);
+            for (auto *v : {&w->r, &w->t, &w->x, &w->b, &w->xs, &w->rs, &w->ts, &w->d}) v->resize(L);
             for (size_t l = 0; l < L; ++l) {
                 const size_t m = (size_t)std::max<int64_t>(lv[l]->n, 1);
                 w->r[l].alloc(m);
@@ -1477,11 +1511,12 @@ struct PCBoomer : PC {
                     w->x[l].alloc(m);
                     w->b[l].alloc(m);
                 }
-                if (!no_cf) {
+                if (!no_cf && relax_type == 0) {
                     w->xs[l].alloc(m);
                     w->rs[l].alloc(m);
                     w->ts[l].alloc(m);
                 }
+                if (relax_type == 3) w->d[l].alloc(m);
             }
             w->cx.alloc(std::max<int64_t>(nco_mine, 1));
             w->cb.alloc(std::max<int64_t>(nco_mine, 1));
@@ -1575,6 +1610,60 @@ struct PCBoomer : PC {
         }
     }
 
+    // the smoother of one level for the relax types Jacobi, l1scaled-Jacobi and Chebyshev, from the
+    // level's host matrix (so nothing hinges on a device summation order): per set the vector m
+    // over all rows, zero off the set (Jacobi: w / a_ii; l1scaled: sign(a_ii) / sum_j |a_ij| in
+    // storage order; 1 where that has a zero denominator), or Chebyshev's 1 / a_ii and
+    // lambda = float(power_lambda(A, dinv, 15)).  No Gauss-Seidel tables are built.
+    void build_relax(BLevel &L, const HostCSR &Al, const std::vector<int8_t> &cf, double weight, Ctx &c) {
+        const int64_t nl = Al.nrows;
+        const DevCSR &Ad = *L.A;
+        L.fused = relax_fused && Ad.sell && Ad.sell->d16 && !Ad.halo && !Ad.sell->nperm && !Ad.sell->b3_nslices;
+        auto up = [&](DBuf<double> &dst, const std::vector<double> &src) {
+            dst.alloc(std::max<size_t>(src.size(), 1));
+            if (!src.empty())
+                HIPCHK(hipMemcpyAsync(dst.p, src.data(), sizeof(double) * src.size(), hipMemcpyHostToDevice, c.st));
+            c.sync();  // (src is a local)
+        };
+        if (relax_type == 3) {
+            const std::vector<double> dinv = amgh::jacobi_dinv(Al);
+            L.lam = amgh::power_lambda(Al, dinv, 15);
+            up(L.dinv, dinv);
+            auto rs = std::make_unique<RelaxSet>();
+            rs->m = nl;
+            L.sets.push_back(std::move(rs));
+            return;
+        }
+        std::vector<double> m(nl, 1.0);
+        for (int64_t i = 0; i < nl; ++i) {
+            double d = 0.0, s = 0.0;
+            for (int64_t k = Al.rp[i]; k < Al.rp[i + 1]; ++k) {
+                if (Al.ci[k] == i) d = Al.v[k];
+                s += std::fabs(Al.v[k]);
+            }
+            if (relax_type == 1) {
+                if (d != 0.0) m[i] = weight / d;
+            } else if (d != 0.0 && s != 0.0) {
+                m[i] = (d > 0.0 ? 1.0 : -1.0) / s;
+            }
+        }
+        for (int g = 0; g < (no_cf ? 1 : 2); ++g) {
+            auto rs = std::make_unique<RelaxSet>();
+            rs->all = no_cf;
+            std::vector<double> mg(m);
+            rs->m = nl;
+            if (!no_cf) {
+                rs->m = 0;
+                for (int64_t i = 0; i < nl; ++i) {
+                    if ((cf[i] == CPT) == (g == 0)) rs->m++;
+                    else mg[i] = 0.0;
+                }
+            }
+            if (rs->m > 0) up(rs->mvec, mg);
+            L.sets.push_back(std::move(rs));
+        }
+    }
+
     // rows [a, a + m) of T (columns unchanged)
     static HostCSR row_range(const HostCSR &T, int64_t a, int64_t m) {
         HostCSR B;
@@ -1628,6 +1717,12 @@ struct PCBoomer : PC {
             throw Error("boomeramg (prefix " + prefix + "): the sharded block's ranks must own contiguous rows");
         K = prm.K;
         no_cf = prm.no_cf;
+        relax_type = prm.relax;
+        cheb_order = prm.cheb_order;
+        cheb_fraction = prm.cheb_fraction;
+        relax_fused = o.flag("pls.amg_relax_fused", true);
+        if (relax_type == 3) no_cf = true;  // Chebyshev: one set of all rows
+        if (dist) boomeramg_refuse_sharded_relax(o, prefix);
         if (!M.sell) build_sell(const_cast<DevCSR &>(M), c);
         const bool view = o.flag("pls.amg_view", false);
         double tm[7] = {0};
@@ -1663,6 +1758,13 @@ struct PCBoomer : PC {
                 upload(R, L->R, c);
                 amg_layout(L->P, c);
                 amg_layout(L->R, c);
+                if (relax_type != 0) {
+                    build_relax(*L, Al, cf, prm.relax_weight, c);
+                    lv.push_back(std::move(L));
+                    c.sync();
+                    tm[5] += now() - t1;
+                    return;
+                }
                 std::vector<int64_t> cst;
                 if (parts.empty()) {
                     cst = chunk_starts(Al.nrows, level_chunks(Al.nrows, prm.chunks, prm.chunk_rows));
@@ -1767,15 +1869,21 @@ struct PCBoomer : PC {
             const bool cols_ok = dist ? true : (L.P.ncols == L.nc && L.R.ncols == L.n);
             if (L.A->nrows != L.n || L.P.nrows != L.n || !cols_ok || L.R.nrows != L.nc || next != L.nc)
                 throw Error("boomeramg: inconsistent hierarchy at level " + std::to_string(l));
-            for (const auto &s : L.sets)
-                if (s->m > 0 && (!s->sgs || s->sgs->n != s->m)) throw Error("boomeramg: smoother size mismatch");
+            for (const auto &s : L.sets) {
+                if (s->m == 0) continue;
+                // Gauss-Seidel: the set's sweep; Jacobi types: m over the level's rows; Chebyshev: 1 / a_ii
+                const bool ok = relax_type == 0   ? s->sgs && s->sgs->n == s->m
+                                : relax_type == 3 ? (int64_t)L.dinv.n >= L.n && s->m == L.n
+                                                  : (int64_t)s->mvec.n >= L.n;
+                if (!ok) throw Error("boomeramg: smoother size mismatch");
+            }
         }
         if (view) {
             fprintf(stderr, "[boomeramg %s] levels %zu%s:", prefix.c_str(), lv.size() + 1, dist ? " (this rank's rows)" : "");
             for (auto &L : lv)
                 fprintf(stderr, " %lld(P nnz %lld, %lld GS chunks)", (long long)L->n, (long long)L->P.nnz,
                         (long long)(L->sets.empty() ? 0 : L->sets[0]->chunks));
-            fprintf(stderr, " coarse %lld\n", (long long)nco);
+            fprintf(stderr, " coarse %lld relax %s\n", (long long)nco, RELAX_NAMES[relax_type]);
             fprintf(stderr,
                     "[boomeramg %s] setup s: download/other %.2f strength %.2f coarsen %.2f interp %.2f RAP %.2f "
                     "smoothers+upload %.2f coarse %.2f (%d threads)\n",
@@ -1835,6 +1943,84 @@ struct PCBoomer : PC {
             }
     }
 
+    // ---- relax types Jacobi, l1scaled-Jacobi, Chebyshev (tests/boomeramg_relax_restatement.py) ----
+    // one step x_new = x + dn, dn = a d + g (m (b - A x)) (kernels.hpp RELAX_*): from x == 0 the
+    // residual is b and no product is formed; else one fused launch where the level's layout
+    // takes it, or the residual and the elementwise step.  x_new is not x.
+    void relax_step(BLevel &L, size_t l, BWork &W, const double *b, const double *x, double *x_new, const double *m,
+                    double *d, double a, double g, int flags, bool x_zero, Ctx &c) {
+        if (x_zero) {
+            launch_relax_step(L.n, b, nullptr, x_new, m, d, a, g, flags | RELAX_X_ZERO, c.st);
+            ++n_unfused;
+        } else if (L.fused) {
+            const DevSELL &S = *L.A->sell;
+            launch_d16_relax(L.n, S.nslices, S.streams(), S.val.p, x, x_new, b, m, d, a, g, flags, c.d16_unroll,
+                             c.d16_xcd, c.st, S.nrows_mapped ? S.rowmap.p : nullptr);
+            ++n_fused;
+        } else {
+            spmv(*L.A, x, W.r[l].p, c, -1.0, 1.0, b);
+            launch_relax_step(L.n, W.r[l].p, x, x_new, m, d, a, g, flags, c.st);
+            ++n_unfused;
+        }
+    }
+
+    // steps of one relax_new call on level L
+    int relax_count(const BLevel &L) const {
+        if (relax_type == 3) return K * cheb_order;
+        int sets = 0;
+        for (const auto &s : L.sets) sets += s->m > 0;
+        return K * sets;
+    }
+
+    // grid_sweeps_all rounds over the sets (down: C then F, up: F then C; Chebyshev: order steps
+    // per round, the recurrence started again).  The steps alternate between x and W.t[l] and
+    // end in x: xin is where the iterate starts (null: zero), x when the count is even, else
+    // W.t[l] (vcycle puts it there), so no copy is launched.
+    void relax_new(size_t l, BWork &W, const double *b, double *x, const double *xin, Ctx &c) {
+        BLevel &L = *lv[l];
+        const int S = relax_count(L);
+        if (S == 0) {
+            if (!xin) launch_set(L.n, 0.0, x, c.st);
+            return;
+        }
+        const bool down = xin == nullptr;
+        double *buf[2] = {x, W.t[l].p};
+        // the buffer step s writes: the last one (s = S - 1) writes x
+        auto dst = [&](int s) { return buf[(S - 1 - s) & 1]; };
+        const double *cur = xin;
+        int s = 0;
+        if (relax_type == 3) {
+            const double lmax = 1.1 * L.lam, lmin = cheb_fraction * lmax;
+            const double th = (lmax + lmin) / 2.0, de = (lmax - lmin) / 2.0;
+            const double sigma = th / de;
+            double *d = W.d[l].p;
+            for (int k = 0; k < K; ++k) {
+                double rho = 1.0 / sigma;
+                for (int q = 0; q < cheb_order; ++q, ++s) {
+                    const int wr = q + 1 < cheb_order ? RELAX_WRITE_D : 0;
+                    if (q == 0) {
+                        relax_step(L, l, W, b, cur, dst(s), L.dinv.p, d, 0.0, 1.0 / th, wr, cur == nullptr, c);
+                    } else {
+                        const double rn = 1.0 / (2.0 * sigma - rho);
+                        relax_step(L, l, W, b, cur, dst(s), L.dinv.p, d, rn * rho, 2.0 * rn / de, RELAX_READ_D | wr,
+                                   false, c);
+                        rho = rn;
+                    }
+                    cur = dst(s);
+                }
+            }
+            return;
+        }
+        for (int k = 0; k < K; ++k)
+            for (size_t g = 0; g < L.sets.size(); ++g) {
+                RelaxSet &st = *L.sets[down ? g : L.sets.size() - 1 - g];
+                if (st.m == 0) continue;
+                relax_step(L, l, W, b, cur, dst(s), st.mvec.p, nullptr, 0.0, 1.0, 0, cur == nullptr, c);
+                cur = dst(s);
+                ++s;
+            }
+    }
+
     void coarse_solve(const double *b, double *x, Ctx &c) {
         if (nco == 0) return;
         if (Clu) Clu->apply(b, x, c);
@@ -1860,6 +2046,17 @@ struct PCBoomer : PC {
         const bool last = (l + 1 == lv.size());
         double *bc = last ? W.cb.p : W.b[l + 1].p;
         double *xc = last ? W.cx.p : W.x[l + 1].p;
+        if (relax_type != 0) {
+            relax_new(l, W, b, x, nullptr, c);
+            spmv(*L.A, x, W.r[l].p, c, -1.0, 1.0, b);
+            spmv(L.R, W.r[l].p, bc, c);
+            vcycle(l + 1, W, bc, xc, c);
+            // the corrected iterate goes where an odd count of post-smoothing steps ends in x
+            double *xs = (relax_count(L) & 1) ? W.t[l].p : x;
+            spmv(L.P, xc, xs, c, 1.0, 1.0, x);
+            relax_new(l, W, b, x, xs, c);
+            return;
+        }
         relax(l, W, b, x, true, true, c);
         lspmv(*L.A, x, W.r[l].p, c, -1.0, 1.0, b);
         lspmv(L.R, W.r[l].p, bc, c);
@@ -1875,11 +2072,32 @@ struct PCBoomer : PC {
             else coarse_solve(x, y, c);
             return;
         }
+        n_fused = n_unfused = 0;
         vcycle(0, work_for(c), x, y, c);
     }
 };
 
 }  // namespace
+
+void boomeramg_refuse_sharded_relax(const Options &o, const std::string &prefix) {
+    const std::string key = prefix + "pc_hypre_boomeramg_relax_type_all";
+    const std::string rt = o.str(key, RELAX_NAMES[0]);
+    if (rt != RELAX_NAMES[0]) throw Error(key + " " + rt + ": a sharded block takes " + RELAX_NAMES[0] + " only");
+}
+
+bool boomeramg_relax_info(const PC *pc, int64_t stats[6], double *lambda, int32_t cap) {
+    const PCBoomer *B = dynamic_cast<const PCBoomer *>(pc);
+    if (!B) return false;
+    stats[0] = B->relax_type;
+    stats[1] = (int64_t)B->lv.size();
+    stats[2] = B->cheb_order;
+    stats[3] = 0;
+    for (const auto &L : B->lv) stats[3] += L->fused ? 1 : 0;
+    stats[4] = B->n_fused;
+    stats[5] = B->n_unfused;
+    for (int32_t l = 0; lambda && l < cap; ++l) lambda[l] = l < (int32_t)B->lv.size() ? B->lv[l]->lam : 0.0;
+    return true;
+}
 
 // hypre on a sharded block (BoomerAMG under mpirun -np G): the gathered block
 // sets up hypre's np = G hierarchy on every rank, each rank keeps its rows

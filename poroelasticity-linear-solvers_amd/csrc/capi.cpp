@@ -790,6 +790,48 @@ int pls_get_asm_rows(pls_handle *hh, const char *prefix, int64_t *ptr, int32_t *
         }
     })
 }
+int pls_get_boomeramg_relax(pls_handle *hh, const char *prefix, int64_t stats[6], double *lambda, int32_t cap) {
+    PLS_TRY({
+        Handle &H = *reinterpret_cast<Handle *>(hh);
+        do_setup(H);
+        const KSP *found = find_ksp(H, prefix, stats, "pls_get_boomeramg_relax");
+        if (lambda == nullptr && cap > 0) throw Error("pls_get_boomeramg_relax: null argument");
+        const bool ok = found->pc && (boomeramg_relax_info(found->pc, stats, lambda, cap) ||
+                                      boomeramg_relax_info(found->pc->unwrapped(), stats, lambda, cap));
+        if (!ok)
+            throw Error("pls_get_boomeramg_relax: the PC with prefix '" + found->prefix + "' is of type " +
+                        (found->pc ? found->pc->type : std::string("none")) + ", not the BoomerAMG stand-in of hypre");
+    })
+}
+int pls_relax_step(pls_handle *hh, const double *m, const double *b, const double *x, double *d, double a, double g,
+                   int32_t fused, double *x_new, int32_t *was_fused) {
+    PLS_TRY({
+        Handle &H = *reinterpret_cast<Handle *>(hh);
+        if (!m || !b || !x || !x_new || !was_fused) throw Error("pls_relax_step: null argument");
+        if (H.A.halo) throw Error("pls_relax_step: one rank only");
+        const int64_t n = H.n;
+        DBuf<double> mi(n), bi(n), xi(n), di(n), yi(n), ri(n);
+        if (!H.vout.p) H.vout.alloc(n);
+        to_internal(H, m, mi.p);
+        to_internal(H, b, bi.p);
+        to_internal(H, x, xi.p);
+        if (d) to_internal(H, d, di.p);
+        build_sell(H.A, H.ctx);
+        const int flags = d ? (RELAX_READ_D | RELAX_WRITE_D) : 0;
+        const DevSELL *S = H.A.sell.get();
+        *was_fused = fused && S && S->d16 && !S->nperm && !S->b3_nslices;
+        if (*was_fused) {
+            launch_d16_relax(n, S->nslices, S->streams(), S->val.p, xi.p, yi.p, bi.p, mi.p, d ? di.p : nullptr, a, g,
+                             flags, H.ctx.d16_unroll, H.ctx.d16_xcd, H.ctx.st, S->nrows_mapped ? S->rowmap.p : nullptr);
+        } else {
+            spmv(H.A, xi.p, ri.p, H.ctx, -1.0, 1.0, bi.p);
+            launch_relax_step(n, ri.p, xi.p, yi.p, mi.p, d ? di.p : nullptr, a, g, flags, H.ctx.st);
+        }
+        HIPCHK(hipGetLastError());
+        if (d) from_internal(H, di.p, d);
+        from_internal(H, yi.p, x_new);
+    })
+}
 int pls_get_bc_columns_stats(pls_handle *hh, const char *prefix, int64_t stats[5]) {
     PLS_TRY({
         Handle &H = *reinterpret_cast<Handle *>(hh);

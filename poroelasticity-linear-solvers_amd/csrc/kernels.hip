@@ -429,6 +429,25 @@ __global__ __launch_bounds__(TPB) void k_cheb_step(int64_t n, const double *__re
     }
 }
 
+// BoomerAMG's Jacobi-type / Chebyshev smoothing step after the row's residual (kernels.hpp
+// RELAX_*): dn = a dold + g (m res), the two products rounded, the a dold term one fma or
+// absent.  The fused launch (k_d16_spmv, D16_AUX_RELAX) and k_relax_step share it, so both
+// give the same bits whatever the compiler contracts elsewhere.
+__device__ __forceinline__ double relax_dn(double res, double m, double g, double a, double dold, bool read_d) {
+    const double u = __dmul_rn(g, __dmul_rn(m, res));
+    return read_d ? fma(a, dold, u) : u;
+}
+__global__ __launch_bounds__(TPB) void k_relax_step(int64_t n, const double *__restrict__ res, const double *x,
+                                                    double *x_new, const double *__restrict__ m, double *d,
+                                                    double a, double g, int flags) {
+    for (int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x; i < n; i += (int64_t)gridDim.x * TPB) {
+        const bool rd = flags & RELAX_READ_D;
+        const double dn = relax_dn(res[i], m[i], g, a, rd ? d[i] : 0.0, rd);
+        if (flags & RELAX_WRITE_D) d[i] = dn;
+        x_new[i] = (flags & RELAX_X_ZERO) ? dn : __dadd_rn(x[i], dn);
+    }
+}
+
 // Polynomial KSP update (richardson, chebyshev; ksp.cpp): out = a pm1 + b pk + c t with
 // t = dinv . z (the Jacobi PC fused in) or t = z.  A null pm1 / pk term is omitted, not
 // multiplied by zero; out may alias pm1 or pk (every entry is read before it is written,
@@ -569,6 +588,10 @@ void launch_pointwise_mult(int64_t n, const double *x, const double *d, double *
 void launch_cheb_step(int64_t n, const double *dinv, const double *r, double *d, double *x, double a, double bc,
                       int flags, hipStream_t st) {
     if (n > 0) k_cheb_step<<<stream_grid(n), TPB, 0, st>>>(n, dinv, r, d, x, a, bc, flags);
+}
+void launch_relax_step(int64_t n, const double *res, const double *x, double *x_new, const double *m, double *d,
+                       double a, double g, int flags, hipStream_t st) {
+    if (n > 0) k_relax_step<<<stream_grid(n), TPB, 0, st>>>(n, res, x, x_new, m, d, a, g, flags);
 }
 void launch_poly_update(int64_t n, double a, const double *pm1, double b, const double *pk, double c,
                         const double *dinv, const double *z, double *out, hipStream_t st) {
@@ -1988,6 +2011,16 @@ __global__ __launch_bounds__(TPB, (G2 == 8 && SEG == 4 && HALO) ? 4 : 1) void k_
         // rowmap: slices hold rows sorted by length inside windows (SELL-C-sigma);
         // the lane's result goes to its row's place
         const int64_t yr = rowmap ? (int64_t)rowmap[row] : row;
+        if (AUX == D16_AUX_RELAX) {
+            // the smoothing step on the row sum (launch_d16_relax): z is b, y is x_new, and the
+            // slots this mode leaves free carry a (alpha), g (beta), m (ghost), d (aux) and the
+            // RELAX_* flags (nlocal); z[yr] - acc has the bits of spmv's alpha -1, beta 1
+            const bool rd = nlocal & RELAX_READ_D;
+            const double dn = relax_dn(z[yr] - acc, ghost[yr], beta, alpha, rd ? aux[yr] : 0.0, rd);
+            if (nlocal & RELAX_WRITE_D) aux[yr] = dn;
+            y[yr] = __dadd_rn(x[yr], dn);
+            return;
+        }
         double r = alpha * acc;
         if (beta != 0.0) r += beta * z[yr];
         y[yr] = r;
@@ -2143,6 +2176,27 @@ void launch_d16_spmv(int64_t nrows, int64_t nslices, const D16Streams &L, const 
                      size_t lds_reserve, const double *aux_init, const D16Wide &W) {
     d16_launch(nrows, nslices, L, dv32, x, y, alpha, beta, z, tag, ghost, nlocal, unroll, d16_xcd, st, slist, rowmap,
                lds_reserve, aux_init ? D16_AUX_INIT : D16_AUX_NONE, const_cast<double *>(aux_init), W);
+}
+// the smoothing step as k_d16_spmv's epilogue (D16_AUX_RELAX): instantiations of their own beside
+// d16_dispatch's (tag 0, no ghost columns, fp64 values), the step's arguments in the free slots
+template <int G2, int SEG>
+static void d16_relax_go(const D16Call<double> &a) {
+    d16_go<G2, 0, false, SEG, D16_AUX_RELAX>(a);
+}
+void launch_d16_relax(int64_t nrows, int64_t nslices, const D16Streams &L, const double *dv, const double *x,
+                      double *x_new, const double *b, const double *m, double *d, double a, double g, int flags,
+                      int unroll, int d16_xcd, hipStream_t st, const int32_t *rowmap) {
+    if (nslices <= 0) return;
+    unsigned grid = grid_for(nslices, TPB / 64);
+    if (d16_xcd) grid = (grid + 7) / 8 * 8;
+    const D16Call<double> c{grid, 0, st, nrows, nslices, L, dv, x, x_new, a, g, b, m, (int32_t)flags, nullptr,
+                            rowmap, d, d16_xcd, D16Wide()};
+    const bool s8 = L.nsegs == 8;
+    switch (unroll) {
+        case 1: s8 ? d16_relax_go<1, 8>(c) : d16_relax_go<1, 4>(c); break;
+        case 2: s8 ? d16_relax_go<2, 8>(c) : d16_relax_go<2, 4>(c); break;
+        default: s8 ? d16_relax_go<4, 8>(c) : d16_relax_go<4, 4>(c); break;
+    }
 }
 
 // ------------------------------------------- D16 with fp32 values (low) ---

@@ -340,6 +340,21 @@ void launch_d16_spmv(int64_t nrows, int64_t nslices, const D16Streams &L, const 
                      int unroll, int d16_xcd, hipStream_t st, const int32_t *slist = nullptr,
                      const int32_t *rowmap = nullptr, size_t lds_reserve = 0, const double *aux_init = nullptr,
                      const D16Wide &W = D16Wide());
+// One smoothing step of BoomerAMG's Jacobi-type and Chebyshev relaxations (boomeramg.cpp):
+//   res = b[i] - sum_j a_ij x[j],  dn = a d[i] + g (m[i] res),  x_new[i] = x[i] + dn
+// RELAX_READ_D: the a d[i] term is formed (else it is absent, not multiplied by zero);
+// RELAX_WRITE_D: d[i] = dn; RELAX_X_ZERO (launch_relax_step only): x is not read, x_new = dn.
+// m res and g (m res) are rounded products, a d[i] + . one fma: relax_dn in kernels.hip.
+constexpr int RELAX_READ_D = 1, RELAX_WRITE_D = 2, RELAX_X_ZERO = 4;
+// ... as one launch over a D16 layout (k_d16_spmv's epilogue D16_AUX_RELAX; fp64 values, no
+// ghost columns, no slice list; rowmap allowed).  x_new must not alias x.
+constexpr int D16_AUX_RELAX = 3;
+void launch_d16_relax(int64_t nrows, int64_t nslices, const D16Streams &L, const double *dv, const double *x,
+                      double *x_new, const double *b, const double *m, double *d, double a, double g, int flags,
+                      int unroll, int d16_xcd, hipStream_t st, const int32_t *rowmap);
+// ... and elementwise from a residual res formed before (any layout): x_new may alias x.
+void launch_relax_step(int64_t n, const double *res, const double *x, double *x_new, const double *m, double *d,
+                       double a, double g, int flags, hipStream_t st);
 // SELL/B3: row triples sharing one column list (FE vector fields), see kernels.hip
 void launch_triple_flags(int64_t n, const int64_t *rp, const int32_t *ci, uint8_t *flag, hipStream_t st);
 int b3_lanes_per_triple();

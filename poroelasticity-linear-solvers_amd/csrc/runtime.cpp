@@ -1470,6 +1470,10 @@ std::unique_ptr<PC> make_pc(const std::string &type, const DevCSR &M, const Opti
                         "for the one-rank ILU applied redundantly)");
         GatheredBlock pre;
         bool gathered = false;
+        if (type == "hypre" && o.str("pls.hypre", "boomeramg") == "boomeramg") {
+            // the Jacobi-type and Chebyshev smoothers are built on one rank's blocks only
+            boomeramg_refuse_sharded_relax(o, prefix);
+        }
         if (type == "hypre" && o.str("pls.hypre", "boomeramg") == "boomeramg" && o.flag("pls.hypre_dist", true)) {
             // BoomerAMG as under mpirun -np G: the np = G hierarchy, each rank smoothing its
             // own rows (Jacobi across ranks); needs ranks owning contiguous rows in rank order

@@ -491,6 +491,13 @@ std::unique_ptr<PC> make_boomeramg_dist(const DevCSR &M, const HostCSR &global, 
                                         const Options &o, const std::string &prefix, Ctx &c);
 void boomeramg_host_level(const HostCSR &A, const Options &o, const std::string &prefix, int64_t level,
                           int64_t &nlevels, int64_t &n, int64_t &nc, std::vector<int8_t> &cf, HostCSR &P);
+// pls_get_boomeramg_relax's values when pc is the BoomerAMG stand-in (else false): stats[0] relax
+// type 0-3, [1] smoothed levels, [2] Chebyshev order, [3] levels on the fused step, [4] fused and
+// [5] elementwise step launches of the last application; lambda[l < cap] the levels' estimates
+// throws, naming the key, when <prefix>pc_hypre_boomeramg_relax_type_all is not the default:
+// the refusal of a sharded block (PCRedundant and make_boomeramg_dist share it)
+void boomeramg_refuse_sharded_relax(const Options &o, const std::string &prefix);
+bool boomeramg_relax_info(const PC *pc, int64_t stats[6], double *lambda, int32_t cap);
 
 // ---------------------------------------------------------------------- KSP --
 struct BcColumns;  // bccols.hpp: the Dirichlet-column split a KSP may own (pls_bc_columns)

@@ -53,7 +53,7 @@ EXPORTS = [
     "pls_matmult_single", "pls_matmult_single_device", "pls_spmv_layout_single", "pls_bench_spmv_single",
     "pls_get_gmres_operator_stats", "pls_get_reuse_rows", "pls_get_asm_stats", "pls_get_asm_rows",
     "pls_get_bc_columns_stats", "pls_get_bc_columns_matrix", "pls_get_d16_share",
-    "pls_get_reuse_wide",
+    "pls_get_reuse_wide", "pls_get_boomeramg_relax", "pls_relax_step",
 ]
 
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p)
@@ -110,6 +110,8 @@ def lib():
     L.pls_get_asm_rows.argtypes = [vp, C.c_char_p, vp, vp]
     L.pls_get_bc_columns_stats.argtypes = [vp, C.c_char_p, vp]
     L.pls_get_bc_columns_matrix.argtypes = [vp, C.c_char_p, vp, vp, vp, vp]
+    L.pls_get_boomeramg_relax.argtypes = [vp, C.c_char_p, vp, vp, i32]
+    L.pls_relax_step.argtypes = [vp, vp, vp, vp, vp, C.c_double, C.c_double, i32, vp, C.POINTER(i32)]
     L.pls_get_reuse_stats.argtypes = [vp, vp]
     L.pls_get_reuse_wide.argtypes = [vp, vp]
     L.pls_get_d16_share.argtypes = [vp, i32, vp]

@@ -340,6 +340,29 @@ class Handle:
         N.check(N.lib().pls_get_asm_rows(self.ptr, prefix.encode(), N.ptr(ptr), N.ptr(rows)))
         return ptr, rows[:s[3]]
 
+    def boomeramg_relax(self, prefix):
+        """(stats, lambda) of the BoomerAMG stand-in with this options prefix (pls_get_boomeramg_relax):
+        stats = (relax type 0 symmetric-SOR/Jacobi / 1 Jacobi / 2 l1scaled-Jacobi / 3 Chebyshev,
+        smoothed levels, Chebyshev order, levels on the fused step, fused step launches and
+        elementwise step launches of the last application); lambda: the levels' eigenvalue
+        estimates (0 for the other types).  Sets the preconditioner up if it was not yet."""
+        s = np.zeros(6, dtype=np.int64)
+        lam = np.zeros(32, dtype=np.float64)
+        N.check(N.lib().pls_get_boomeramg_relax(self.ptr, prefix.encode(), N.ptr(s), N.ptr(lam), 32))
+        return tuple(int(v) for v in s), lam[:int(s[1])].copy()
+
+    def relax_step(self, m, b, x, d=None, a=0.0, g=1.0, fused=True):
+        """One smoothing step on the outer operator A (pls_relax_step; a diagnostic):
+        x_new = x + dn, dn = a d + g (m (b - A x)); d None: no a d term.  Returns
+        (x_new, d_new or None, was_fused)."""
+        m, b, x = (np.ascontiguousarray(v, dtype=np.float64) for v in (m, b, x))
+        dn = None if d is None else np.array(d, dtype=np.float64)
+        y = np.empty_like(x)
+        wf = C.c_int32()
+        N.check(N.lib().pls_relax_step(self.ptr, N.ptr(m), N.ptr(b), N.ptr(x), None if dn is None else N.ptr(dn),
+                                       float(a), float(g), int(bool(fused)), N.ptr(y), C.byref(wf)))
+        return y, dn, bool(wf.value)
+
     def bc_columns_stats(self, prefix):
         """(mode: 0 keep, 1 lift, 2 drop; constrained rows; entries moved to C; rows of C; bytes the
         KSP holds for K' and C) of the inner solver with this options prefix (<prefix>pls_bc_columns,
