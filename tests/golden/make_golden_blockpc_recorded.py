@@ -39,7 +39,7 @@ def _spec():
 
 def _options(params_update, prefixes, preonly=True, extra=None):
     from lib.handle import params_to_options
-    from test_gpu_sweep_choice import GLOBAL, PARAMS
+    from sweep_choice_cases import GLOBAL, PARAMS
     db = dict(GLOBAL)
     for pre in prefixes:
         if preonly:
@@ -94,7 +94,7 @@ def run_case(name):
     elif name == "twoway-fieldsplit":
         from lib.handle import params_to_options
         from test_gpu_parity import FS_INEXACT, FS_PARAMS
-        from test_gpu_sweep_choice import PARAMS
+        from sweep_choice_cases import PARAMS
         opts = dict(FS_INEXACT, **{"fp_fieldsplit_0_ksp_type": "preonly", "fp_fieldsplit_0_pc_type": "ilu"})
         opts.update(params_to_options(dict(PARAMS, **FS_PARAMS)))
         h = _synthetic(opts)
