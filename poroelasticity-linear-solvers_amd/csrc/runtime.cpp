@@ -1171,11 +1171,15 @@ std::unique_ptr<PC> make_lu(const DevCSR &M, const Options &o, Ctx &c) {
     if (path == "band") {
         int64_t kl = 0, ku = 0;
         csr_bandwidths(M, kl, ku, c);
-        // band tiles + the SPIKE spikes (nb x (bl + bu) tiles): ~2x the band.  Default cap:
-        // 3/4 of the card's HBM (288 GB per MI355X: the 2-D footing N=128 Schur block's
-        // 95 GB band + 95 GB of spikes fit; an allocation that then fails is reported),
-        // pls.lu_band_max_gb overrides
-        return std::make_unique<PCBandLU>(M, kl, ku, c, o.integer("pls.band_spike_plen", -1));
+        // band tiles + the SPIKE spikes (nb x (bl + bu) tiles): ~2x the band (288 GB per
+        // MI355X: the 2-D footing N=128 Schur block's 95 GB band + 95 GB of spikes fit).
+        // There is no cap and no option that sets one: an allocation that fails is reported
+        auto pc = std::make_unique<PCBandLU>(M, kl, ku, c, o.integer("pls.band_spike_plen", -1));
+        if (o.flag("pls.lu_view", false))
+            fprintf(stderr, "[band lu] n %lld: tile rows %lld, bl %lld, bu %lld, spike plen %lld, partitions %lld\n",
+                    (long long)M.nrows, (long long)pc->nb, (long long)pc->bl, (long long)pc->bu, (long long)pc->plen,
+                    (long long)(pc->plen > 0 ? (pc->nb + pc->plen - 1) / pc->plen : 1));
+        return pc;
     }
     // the envelope (profile) LU: exact, level-scheduled
     PCILU::Config cfg = PCILU::Config::from_options(o, "", 0);
